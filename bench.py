@@ -19,6 +19,14 @@ content-preparation rate (tsg_prepare_batch).
   python bench.py [--gpus N --steps K --warmup W --config 1|2|3|5 --gb G]
   torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
 
+A plain run sets up, warms up, times the K steps and prints the result line
+(`value`, `ms_per_step`, the steps' own K1 / link / breakdown figures).  The
+side figures named above and below (HBM-resident rate, host-feed ceiling,
+content-preparation rate, the layer-tar / fs-tree / per-file legs, GPU CR
+strip, cpu_baseline and parity) are measured only with --full.
+--dump-outputs DIR writes what the last timed step returned as DIR/*.npy
+(dump_outputs), for comparing two builds output for output.
+
 Multi-GPU: each rank scans its own file shard (seed + rank, weak scaling) on
 its own GPU; there is no collective on the data path (gloo carries only the
 barrier and the max-time reduction).  Rank 0 prints one JSON line.
@@ -583,6 +591,56 @@ def _segment_bytes():
     return int(v) if v and int(v) >= 4096 else 4 << 30
 
 
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs writes at most this much in all
+
+
+def _digest48(b):
+    """48 bits of SHA-256 as a float64 (exact: below 2**53)."""
+    import hashlib
+    return float(int.from_bytes(hashlib.sha256(b).digest()[:6], "big"))
+
+
+def dump_outputs(results, out_dir, suffix="", seed=0, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: the step's results (one types.Secret dict per file, as
+    tsg_result_json gives them) as float64 arrays under out_dir, so that two
+    builds can be compared output for output:
+      findings_per_file  [files]        findings of each file
+      file_digest        [files]        digest of the file's whole result (path and every finding field)
+      findings           [findings, 8]  one row per finding in result order: file index, StartLine, EndLine,
+                                        code lines, digest of RuleID, of Severity + Category + Title, of Match,
+                                        of the whole finding (code lines included)
+    Strings enter as 48-bit SHA-256 digests, exact in float64.  Arrays that
+    would pass max_bytes in all are cut to a fixed sample of rows (seeded,
+    sorted), the same for every run with the same arguments; the sampled row
+    numbers are then written beside them as <name>_rows."""
+    def canon(o):
+        return json.dumps(o, sort_keys=True, ensure_ascii=True, separators=(",", ":")).encode("ascii")
+    per_file = np.array([len(s["Findings"]) for s in results], dtype=np.float64)
+    fdig = np.array([_digest48(canon(s)) for s in results], dtype=np.float64)
+    rows = []
+    for i, s in enumerate(results):
+        for f in s["Findings"]:
+            rows.append((i, f["StartLine"], f["EndLine"], len(f["Code"]["Lines"] or ()),
+                         _digest48(canon(f["RuleID"])),
+                         _digest48(canon([f["Severity"], f["Category"], f["Title"]])),
+                         _digest48(canon(f["Match"])), _digest48(canon(f))))
+    arrays = {"findings_per_file": per_file, "file_digest": fdig,
+              "findings": np.array(rows, dtype=np.float64).reshape(len(rows), 8)}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > max_bytes:
+        keep = max_bytes / (total + 8 * sum(len(a) for a in arrays.values()))
+        rng = np.random.default_rng(seed)
+        for name in list(arrays):
+            a = arrays[name]
+            pick = np.sort(rng.choice(len(a), size=int(len(a) * keep), replace=False))
+            arrays[name] = a[pick]
+            arrays[name + "_rows"] = pick.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
@@ -619,10 +677,20 @@ def main():
                     help="1: also time the per-file drop-in (small batches, the Scan queue at --parallel 5 and at "
                          "the rank's core count); default: config 1 only")
     ap.add_argument("--json-out", default="")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side legs: host content preparation rate, host-feed "
+                         "ceiling, layer-tar / fs-tree / per-file legs of their configs, the HBM-resident leg and "
+                         "GPU CR strip, the CPU baselines and the oracle parity check (exit 1 unless diff = 0); "
+                         "without it the run sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned (every file's types.Secret) as DIR/<name>.npy "
+                         "float64 arrays (dump_outputs)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="ranks only report their wiring (rank, device, device_mask) and exit: the launcher's "
                          "CPU test")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     gb = args.gb if args.gb is not None else (1.0 if args.config == 1 else 10.0)
 
     if "WORLD_SIZE" not in os.environ and (args.gpus or 1) > 1:
@@ -706,11 +774,12 @@ def main():
     # host content preparation over the files as read (SecretAnalyzer.Required +
     # IsBinary + CR strip + .pyc extraction, tsg_prepare_batch); for config 3
     # its output IS the scanned batch (bytes counted after gating)
-    # (measured on rank 0 only for configs other than 3: its output is a second
-    # copy of the batch, which every rank of an 8-GPU node need not hold)
+    # (for configs other than 3 it is a side leg, measured under --full on
+    # rank 0 only: its output is a second copy of the batch, which every rank
+    # of an 8-GPU node need not hold)
     prep_gbps, nk = None, ctypes.c_uint32()
     hpb = ctypes.c_void_p()
-    if args.config == 3 or rank == 0:
+    if args.config == 3 or (args.full and rank == 0):
         paths, lens, _keep = _lib.pack_paths(corpus.paths)
         # config 3 prepares straight into pinned memory: its output is the batch
         fo, _fkeep = _lib.feed_opts(threads=args.threads, pinned=args.config == 3)
@@ -819,11 +888,16 @@ def main():
     launches = max(1, int(stats[-1]["k1_launches"]))
     segments = max(1, int(stats[-1]["pieces"]))
     groups = max(1, launches // segments)
-    if nshards > 1:                    # config 4: the parity legs below check the first shard's batch
-        L.tsg_result_free(last)
-        last = scan_one(batch)
-    gpu_results = _lib.result_json(last)
+    gpu_results = _lib.result_json(last)    # what the last timed step returned (config 4: its last shard)
     L.tsg_result_free(last)
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(gpu_results, args.dump_outputs, "" if rank == 0 else "_rank%d" % rank, args.seed)
+        log("outputs of the last timed step written to %s: %s" % (args.dump_outputs, dumped))
+    if nshards > 1:                    # config 4: the figures and legs below are of the first shard's batch
+        last = scan_one(batch)
+        gpu_results = _lib.result_json(last)
+        L.tsg_result_free(last)
     findings = sum(len(s["Findings"]) for s in gpu_results)
     rules_hit = sorted({f["RuleID"] for s in gpu_results for f in s["Findings"]})
     k1_gbps = nbytes / (k1_ms / 1e3) / 1e9
@@ -920,31 +994,37 @@ def main():
                       "prepare_kept_files": nk.value if prep_gbps is not None else None},
         "cpu_baseline": None,
         "parity": None,
+        "full": bool(args.full),
+        **({"dumped_outputs": dumped} if dumped else {}),
     }
 
-    # host-feed ceiling: the same segmented upload with no kernels, every rank
-    # at once after a barrier (the ranks share host DRAM and the root
-    # complexes: the concurrent sum is the node's feed ceiling)
-    fms = ctypes.c_double()
-    if dist:
-        dist.barrier()
-    _lib.check(L.tsg_feed_probe(eng, batch.ptr, batch.nbytes, ctypes.byref(fms)))
-    my_ceiling = batch.nbytes / (fms.value / 1e3) / 1e9
-    mine = {"rank": rank, "device": device, "numa": numa, "ceiling_gbps": round(my_ceiling, 2),
+    # everything below `value`'s own figures is a side leg, run under --full
+    mine = {"rank": rank, "device": device, "numa": numa,
             "link_gbps": round(nbytes / (h2d_ms / 1e3) / 1e9, 2), "step_ms": round(elapsed / args.steps * 1e3, 3),
             "k1_ms": round(k1_ms, 3), "k2_ms": round(k2_ms, 3), "h2d_ms": round(h2d_ms, 3),
             "host_confirm_ms": round(host_ms, 3), "bytes": nbytes}
+    if args.full:
+        # host-feed ceiling: the same segmented upload with no kernels, every rank
+        # at once after a barrier (the ranks share host DRAM and the root
+        # complexes: the concurrent sum is the node's feed ceiling)
+        fms = ctypes.c_double()
+        if dist:
+            dist.barrier()
+        _lib.check(L.tsg_feed_probe(eng, batch.ptr, batch.nbytes, ctypes.byref(fms)))
+        my_ceiling = batch.nbytes / (fms.value / 1e3) / 1e9
+        mine["ceiling_gbps"] = round(my_ceiling, 2)
     ranks = gather_ranks(dist, world, mine)
-    out["host_feed"]["ceiling_gbps"] = round(my_ceiling, 2)
-    out["host_feed"]["ceiling_gbps_all_ranks"] = round(sum(r["ceiling_gbps"] for r in ranks), 2)
     out["per_rank"] = ranks
-    out["host_feed"]["note"] = ("ceiling_gbps: tsg_feed_probe on rank 0, the step's segmented pinned upload with no "
-                                "kernels; ceiling_gbps_all_ranks: the same probe on every rank at once after a "
-                                "barrier, summed (the node's concurrent host-feed ceiling to set `value` against); "
-                                "prepare_gbps: tsg_prepare_batch over the raw files")
-    log("host-feed ceiling (segmented pinned upload, no kernels): %.1f GB/s on rank 0, %.1f GB/s over %d ranks at "
-        "once" % (my_ceiling, out["host_feed"]["ceiling_gbps_all_ranks"], world))
-    if args.config == 3 and rank == 0:
+    if args.full:
+        out["host_feed"]["ceiling_gbps"] = round(my_ceiling, 2)
+        out["host_feed"]["ceiling_gbps_all_ranks"] = round(sum(r["ceiling_gbps"] for r in ranks), 2)
+        out["host_feed"]["note"] = ("ceiling_gbps: tsg_feed_probe on rank 0, the step's segmented pinned upload with "
+                                    "no kernels; ceiling_gbps_all_ranks: the same probe on every rank at once after "
+                                    "a barrier, summed (the node's concurrent host-feed ceiling to set `value` "
+                                    "against); prepare_gbps: tsg_prepare_batch over the raw files")
+        log("host-feed ceiling (segmented pinned upload, no kernels): %.1f GB/s on rank 0, %.1f GB/s over %d ranks "
+            "at once" % (my_ceiling, out["host_feed"]["ceiling_gbps_all_ranks"], world))
+    if args.full and args.config == 3 and rank == 0:
         # the image path's host feed from a layer tar: walker.LayerTar.Walk +
         # Required + content prep into pinned memory (tsg_prepare_layer_tar)
         tgb, tfiles, tkept, tdt, tstream = layer_tar_rate(L, sc, batch, 2e9, args.threads)
@@ -956,7 +1036,7 @@ def main():
             "(tar -> findings, tsg_scan_layer_stream): %.1f GB/s = %.2f of the walk rate" % (
                 args.threads, tgb, tstream["gbps"], tstream["of_walk_rate"]))
 
-    if rank == 0 and (args.tree == 1 or (args.tree == -1 and args.config == 1)):
+    if args.full and rank == 0 and (args.tree == 1 or (args.tree == -1 and args.config == 1)):
         tr = tree_feed(L, sc, batch, args.threads, args.tree_dir)
         out["host_feed"]["tree"] = tr
         out["host_feed"]["tree_read_gbps"] = {"warm": tr["warm"]["gbps"], "cold": tr["cold"]["gbps"]}
@@ -971,7 +1051,7 @@ def main():
             print("[bench] fs-tree feed differs from the in-memory preparation", file=sys.stderr, flush=True)
             sys.exit(1)
 
-    if rank == 0 and (args.per_file == 1 or (args.per_file == -1 and args.config == 1)):
+    if args.full and rank == 0 and (args.per_file == 1 or (args.per_file == -1 and args.config == 1)):
         out["small_batch"] = small_batches(L, eng, batch)
         out["per_file"] = per_file_queue(sc, batch, (5, cores))
         sb = out["small_batch"]
@@ -981,7 +1061,7 @@ def main():
             "%s %.3f GB/s (%.1f files/batch)" % (k, v["gbps"], v["mean_batch_files"])
             for k, v in out["per_file"].items() if isinstance(v, dict)))
 
-    if not args.no_resident:
+    if args.full and not args.no_resident:
         # the same batch already resident in HBM (reported, never `value`)
         d_data = torch.empty(batch.nbytes + 64, dtype=torch.uint8, device="cuda:%d" % device)
         d_data.copy_(torch.from_numpy(batch.view), non_blocking=False)
@@ -1062,7 +1142,7 @@ def main():
         torch.cuda.empty_cache()
 
     failed = False
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         procs = args.cpu_procs or cores
         idx = pick_sample(batch.offsets, int(args.cpu_sample_mb * 1e6), args.seed)
         items = [(batch.paths[i], batch.file(i), bool(batch.binary[i]) if batch.binary is not None else False)

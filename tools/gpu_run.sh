@@ -6,7 +6,7 @@
 # gpurun_out/TAG/.  Steps:
 #   tests[:PYTEST-ARGS]        pytest -m gpu (default: the whole GPU suite)
 #   smoke                      __graft_entry__.smoke()
-#   bench[:NAME[:ARGS]]        python bench.py ARGS > NAME.json (NAME default bench)
+#   bench[:NAME[:ARGS]]        python bench.py ARGS > NAME.json (NAME default bench; without ARGS: --full)
 #   prof[:NAME[:ARGS]]         rocprofv3 --kernel-trace --stats of bench.py ARGS
 #   pmc[:NAME[:ARGS]]          tools/pmc_k1.sh passes over bench.py ARGS
 #   traffic[:NAME[:ARGS]]      tools/pmc_traffic.sh (FETCH_SIZE / WRITE_SIZE) over bench.py ARGS
@@ -38,12 +38,12 @@ for STEP in "$@"; do
       cat $OUT/smoke.log ;;
     bench)
       N=${NAME:-bench}
-      timeout -k 10 900 python -u bench.py $ARGS > $OUT/$N.json 2> $OUT/$N.log || { tail -30 $OUT/$N.log; exit 1; }
+      timeout -k 10 900 python -u bench.py ${ARGS:---full} > $OUT/$N.json 2> $OUT/$N.log || { tail -30 $OUT/$N.log; exit 1; }
       grep -E 'step|ceiling|resident|parity|cpu base|launcher' $OUT/$N.log ;;
     prof)
       N=${NAME:-prof}
       timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $ROOT/$OUT/$N -o $N -- \
-        python3 $ROOT/bench.py ${ARGS:---no-cpu-baseline --steps 3} > $OUT/$N.json 2> $OUT/$N.log \
+        python3 $ROOT/bench.py ${ARGS:---full --no-cpu-baseline --steps 3} > $OUT/$N.json 2> $OUT/$N.log \
         || { tail -20 $OUT/$N.log; exit 1; }
       grep step $OUT/$N.log ;;
     pmc)
