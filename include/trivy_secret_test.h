@@ -98,6 +98,21 @@ int tsg_test_multi_driver_model(uint32_t ndevices, uint32_t nsegments, int32_t f
  * by tsg_scan_batch. */
 int tsg_test_inject_segment_failures(tsg_engine* e, uint32_t n);
 
+/* Test hook for the wire packing (csrc/wirepack.h): packs src[0, n) as one
+ * strip on the host -- path 0: the CPU's best, 1: scalar, 2: AVX2 (scalar on a
+ * CPU without it; *path_used tells which ran) -- into packed (packed_cap
+ * bytes; n + 8 always suffices) and table (one entry per 4096-byte block:
+ * offset in packed, bit 31 set for a block sent unchanged); *packed_len = the
+ * packed bytes.  back (n bytes, may be NULL) receives the host unpack of the
+ * result.  Never used by tsg_scan_batch. */
+int tsg_test_wire_pack(const uint8_t* src, size_t n, int path, uint8_t* packed, size_t packed_cap, uint32_t* table,
+                       size_t* packed_len, int* path_used, uint8_t* back);
+/* Test hook: uploads a packed strip to HIP device 0, runs the unpack kernel
+ * and reads the n restored bytes back into out; fails if the kernel wrote
+ * past them.  Never used by tsg_scan_batch. */
+int tsg_test_wire_unpack_device(const uint8_t* packed, size_t packed_len, const uint32_t* table, size_t n,
+                                uint8_t* out);
+
 /* The same two pipelines with the CPU model of the GPU passes as the scan
  * stage (tsg_scan_table_model's); tests only, never the product path. */
 int tsg_scan_layer_stream_model(const tsg_ruleset* rs, tsg_read_fn read, void* user, const tsg_feed_opts* opts,

@@ -32,7 +32,9 @@ class TsgStats(ctypes.Structure):
                 ("k1_blocks", ctypes.c_uint32), ("k1_threads", ctypes.c_uint32), ("chunk_bytes", ctypes.c_uint32),
                 ("table_in_lds", ctypes.c_int32), ("gpu_wall_ms", ctypes.c_double),
                 ("pieces", ctypes.c_uint32), ("k1_launches", ctypes.c_uint32), ("devices", ctypes.c_uint32),
-                ("feed_ms", ctypes.c_double)]
+                ("feed_ms", ctypes.c_double),
+                ("wire_bytes", ctypes.c_uint64), ("packed_strips", ctypes.c_uint32), ("raw_strips", ctypes.c_uint32),
+                ("pack_ms", ctypes.c_double)]
 
 
 # (name, restype, argtypes) for every entry point declared in include/trivy_secret.h
@@ -91,6 +93,11 @@ SIGNATURES = [
     ("tsg_test_engine_footprint", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
                                                   ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
     ("tsg_test_inject_segment_failures", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
+    ("tsg_test_wire_pack", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p,
+                                           ctypes.c_size_t, ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t),
+                                           ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]),
+    ("tsg_test_wire_unpack_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                                    ctypes.c_size_t, ctypes.c_void_p]),
     ("tsg_scan_host_reference", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                                 c_char_pp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                                 ctypes.POINTER(ctypes.c_void_p)]),

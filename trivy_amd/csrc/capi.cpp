@@ -433,6 +433,8 @@ int tsg_result_stats(const tsg_result* r, tsg_stats* out) {
   out->k1_launches = s.k1_launches;
   out->devices = s.devices;
   out->feed_ms = s.feed_ms;
+  out->wire_bytes = s.wire_bytes; out->packed_strips = s.packed_strips; out->raw_strips = s.raw_strips;
+  out->pack_ms = s.pack_ms;
   return TSG_OK;
   TSG_API_CATCH
 }
@@ -782,6 +784,38 @@ int tsg_test_inject_segment_failures(tsg_engine* e, uint32_t n) {
   TSG_API_TRY
   if (!e) return fail(TSG_ERR_INVALID, "engine is NULL");
   e->eng->inject_segment_failures(n);
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_test_wire_pack(const uint8_t* src, size_t n, int path, uint8_t* packed, size_t packed_cap, uint32_t* table,
+                       size_t* packed_len, int* path_used, uint8_t* back) {
+  TSG_API_TRY
+  if ((!src && n) || !table || !packed_len || (!packed && packed_cap)) return fail(TSG_ERR_INVALID, "NULL argument");
+  if (path < 0 || path > 2 || n > kWireMaxStrip) return fail(TSG_ERR_INVALID, "path or length out of range");
+  std::vector<uint8_t> buf(wire_bound(n));
+  std::vector<uint32_t> tab(wire_blocks(n) + 1);
+  const size_t pl = wire_pack(src, n, buf.data(), tab.data(), path);
+  *packed_len = pl;
+  if (path_used) *path_used = path != kWireScalar && wire_have_avx2() ? kWireAvx2 : kWireScalar;
+  if (pl > packed_cap) return fail(TSG_ERR_INVALID, "packed_cap is too small");
+  if (pl) memcpy(packed, buf.data(), pl);
+  memcpy(table, tab.data(), wire_blocks(n) * sizeof(uint32_t));
+  if (back) {
+    // (from an exact-size copy: the reference unpack reads nothing past the packed bytes)
+    std::vector<uint8_t> exact(buf.begin(), buf.begin() + pl);
+    wire_unpack(exact.data(), tab.data(), n, back);
+  }
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_test_wire_unpack_device(const uint8_t* packed, size_t packed_len, const uint32_t* table, size_t n,
+                                uint8_t* out) {
+  TSG_API_TRY
+  if (n && (!packed || !table || !out)) return fail(TSG_ERR_INVALID, "NULL argument");
+  const char* msg = "";
+  if (!wire_unpack_device_probe(packed, packed_len, table, n, out, &msg)) return fail(TSG_ERR_INTERNAL, msg);
   return TSG_OK;
   TSG_API_CATCH
 }

@@ -9,10 +9,12 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "prefilter.h"
 #include "scanner.h"
+#include "wirepack.h"
 
 namespace tsg {
 
@@ -25,6 +27,11 @@ struct ScanStats {
   uint32_t k1_launches = 0;             // K1 launches (segments x scan-DFA groups)
   uint32_t devices = 1;                 // devices that took part
   double feed_ms = 0;                   // wall time from the first upload to the last segment's upload done
+  // wire packing (wirepack.h): bytes that crossed the link for the batch's
+  // data, strips sent packed / as they are, the packer threads' summed busy time
+  uint64_t wire_bytes = 0;
+  uint32_t packed_strips = 0, raw_strips = 0;
+  double pack_ms = 0;
 };
 
 struct BatchInput {
@@ -47,6 +54,7 @@ struct GpuOut;
 struct CallCtx;
 struct K1Chain;
 struct StageIn;
+struct WireFeed;
 
 // One engine = the compiled ruleset's device tables on every selected device.
 // scan() is reentrant: each call takes its own lane (HIP streams + scratch
@@ -138,10 +146,32 @@ class Engine {
   // leaves the critical chain: config 2 1632 -> 1862 GB/s, 1 GB of config-1
   // files 482 -> 570 (profiles/r5p_resident_variants.log).
   int resident_drivers_ = 2;
-  int chain_k1_ = 1;
+  int chain_k1_ = 1;                    // K1Chain: 0 = next K1 after this K2, 1 = after this K1, 2 = no wait (TSG_CHAIN_K1)
   uint32_t k1_reserve_cus_ = 0;         // K1Chain pieces: CUs left out of K1's grid for the previous piece's K2 / readback (TSG_K1_RESERVE_CUS)
-  bool readback_dma_ = false;
-  bool file_index_ = true;              // K1 range starts' files from a per-64-KiB index (TSG_K1_FILE_INDEX)           // K1Chain pieces read back by DMA copies instead of tsg_readback (TSG_READBACK_DMA)                    // K1Chain: 0 = next K1 after this K2, 1 = after this K1, 2 = no wait (TSG_CHAIN_K1)
+  bool readback_dma_ = false;           // K1Chain pieces read back by DMA copies instead of tsg_readback (TSG_READBACK_DMA)
+  bool file_index_ = true;              // K1 range starts' files from a per-64-KiB index (TSG_K1_FILE_INDEX)
+  // Wire packing of uploaded batches (wirepack.h; TSG_WIRE_PACK 0 = off, 1 =
+  // packers race the link, force = every strip waits for a packer).  The
+  // packer threads belong to the engine: started on the first eligible scan,
+  // parked on wire_cv_ between scans, serving one scan at a time (wire_job_).
+  int wire_mode_ = 0;                   // 0 off, 1 race, 2 force
+  int wire_threads_n_ = -1;             // TSG_WIRE_PACK_THREADS; -1 = the engine's threads - 2, at most 16
+  // bytes per strip (TSG_WIRE_STRIP_BYTES, a multiple of 4096).  Config 2, 14
+  // packers: 4 MiB 198.7 ms per step, 8 MiB 179.2, 16 MiB 169.9-170.2, 32 MiB
+  // 165.0, 64 MiB 162.4-163.1 (single copy per segment: 179.0-179.2): every
+  // strip copy costs the link about 14 us; 64 MiB with the packers a segment
+  // ahead 160.9-161.1 (profiles/wirepack_c2.json).  Each packer holds a pinned
+  // staging slot and a device twin of this size.
+  uint64_t wire_strip_ = 64ull << 20;
+  std::mutex wire_mu_;
+  std::condition_variable wire_cv_;
+  std::vector<std::thread> wire_threads_;
+  WireFeed* wire_job_ = nullptr;
+  uint64_t wire_gen_ = 0;
+  int wire_active_ = 0;                 // packers inside wire_job_
+  bool wire_busy_ = false;              // a scan holds the packers
+  bool wire_stop_ = false;
+  void wire_packer_main();
   // K1Chain drivers poll their readback event yielding instead of sleeping
   // 10 us (TSG_POLL_YIELD), and the confirmer polls the job queue up to
   // pop_spin_us_ before it sleeps (TSG_POP_SPIN_US): a wake-up under the busy

@@ -1515,6 +1515,7 @@ struct StageIn {
   const uint8_t* off_src = nullptr; uint8_t* off_dst = nullptr; uint64_t off_bytes = 0;
 };
 constexpr uint64_t kDirectStageBytes = 1u << 20;     // batches up to this size (and pinned) are staged by the prologue
+constexpr int kWirePackDefault = 1;            // TSG_WIRE_PACK unset: 1 = packers race the link (wirepack.h)
 
 struct Lane {
   int device = 0;
@@ -1524,6 +1525,18 @@ struct Lane {
   const std::atomic<bool>* pool_idle = nullptr; // set by a scan's driver: its confirm pool has no work
   hipEvent_t up_begin[2] = {}, up_done[2] = {}; // upload ring slot: H2D start / done (copy stream)
   hipEvent_t anchor = nullptr;                   // TSG_HOST_PROFILE: start of a scan() on the copy stream
+  // wire packing (WireFeed): pinned staging slots the packers fill, each with
+  // a device landing twin; the stream the unpack kernels run on; events of the
+  // raw strip copies in flight and of a segment's last copy
+  struct WireSlot {
+    uint8_t* h = nullptr; uint8_t* d = nullptr;
+    hipEvent_t copied = nullptr, unpacked = nullptr;
+  };
+  std::vector<WireSlot> wire;
+  size_t wire_cap = 0;
+  hipStream_t unpack = nullptr;
+  hipEvent_t wire_raw_ev[4] = {};
+  hipEvent_t wire_copies_done[2] = {};
   uint8_t* ring[2] = {nullptr, nullptr};
   size_t ring_cap[2] = {0, 0};
   uint64_t* d_off = nullptr; size_t d_off_cap = 0;
@@ -1553,6 +1566,7 @@ struct Lane {
   size_t hit_cap = 1 << 20, cand_cap = 1 << 18, over_cap = 1 << 18;
   double k2_maxr_per_byte = 0;                       // K2 grid of the next segment: the last one's fullest region
   uint64_t k2_over_est = 0;                          // per byte, and its overflow hit count
+  void free_wire();
   ~Lane();
 };
 
@@ -1630,10 +1644,26 @@ DeviceTables::~DeviceTables() {
   }
 }
 
+void Lane::free_wire() {
+  for (WireSlot& w : wire) {
+    if (w.h) hipHostFree(w.h);
+    if (w.d) hipFree(w.d);
+    if (w.copied) hipEventDestroy(w.copied);
+    if (w.unpacked) hipEventDestroy(w.unpacked);
+  }
+  wire.clear();
+  wire_cap = 0;
+}
+
 Lane::~Lane() {
   hipSetDevice(device);
   if (compute) hipStreamSynchronize(compute);
   if (copy) hipStreamSynchronize(copy);
+  if (unpack) hipStreamSynchronize(unpack);
+  free_wire();
+  for (auto& e : wire_raw_ev) if (e) hipEventDestroy(e);
+  for (auto& e : wire_copies_done) if (e) hipEventDestroy(e);
+  if (unpack) hipStreamDestroy(unpack);
   for (uint64_t* h : h_off_pin) if (h) hipHostFree(h);
   for (PinnedBuf* b : {&rb_bh, &rb_c2, &rb_cands, &rb_ff, &rb_nl}) if (b->p) hipHostFree(b->p);
   void* ps[] = {ring[0], ring[1], off_slot[0], off_slot[1], d_off, d_kw, d_hits, d_over, d_bh, d_cands, d_nl, d_cf, d_ff, d_ob, d_cnt, d_k2s, d_cr, d_fidx};
@@ -1853,6 +1883,8 @@ void add_stats(ScanStats* a, const ScanStats& s) {
   a->hits += s.hits; a->candidates += s.candidates; a->k1_launches += s.k1_launches;
   a->k1_blocks = s.k1_blocks; a->k1_threads = s.k1_threads; a->chunk_bytes = s.chunk_bytes;
   a->table_in_lds = s.table_in_lds;
+  a->wire_bytes += s.wire_bytes; a->packed_strips += s.packed_strips; a->raw_strips += s.raw_strips;
+  a->pack_ms += s.pack_ms;
 }
 
 }  // namespace
@@ -1914,6 +1946,13 @@ std::unique_ptr<Engine> Engine::create(std::shared_ptr<const Ruleset> rs, const 
   if (const char* c = std::getenv("TSG_POLL_YIELD")) e->poll_yield_ = std::atoi(c) != 0;
   if (const char* c = std::getenv("TSG_POP_SPIN_US")) e->pop_spin_us_ = std::max(0, std::min(std::atoi(c), 100000));
   if (const char* c = std::getenv("TSG_HOST_PROFILE")) e->host_profile_ = std::atoi(c) != 0;
+  e->wire_mode_ = kWirePackDefault;
+  if (const char* c = std::getenv("TSG_WIRE_PACK")) e->wire_mode_ = std::strcmp(c, "force") == 0 ? 2 : std::atoi(c) != 0 ? 1 : 0;
+  if (const char* c = std::getenv("TSG_WIRE_PACK_THREADS")) e->wire_threads_n_ = std::max(0, std::min(16, std::atoi(c)));
+  if (const char* c = std::getenv("TSG_WIRE_STRIP_BYTES")) {
+    const long long v = std::atoll(c);
+    if (v >= kWireBlock) e->wire_strip_ = std::min<uint64_t>(static_cast<uint64_t>(v) / kWireBlock * kWireBlock, kWireMaxStrip);
+  }
   if (e->host_profile_) g_scan_prof_on.store(true, std::memory_order_relaxed);
   if (const char* c = std::getenv("TSG_K1_TAIL_ROUNDS")) {
     const int v = std::atoi(c);
@@ -1941,6 +1980,12 @@ std::unique_ptr<Engine> Engine::create(std::shared_ptr<const Ruleset> rs, const 
 }
 
 Engine::~Engine() {
+  {
+    std::lock_guard<std::mutex> lk(wire_mu_);
+    wire_stop_ = true;
+  }
+  wire_cv_.notify_all();
+  for (std::thread& t : wire_threads_) t.join();
   if (k2_stats_ && !k2s_.empty()) {
     // TSG_K2_STATS: per-rule K2 work of every scan of this engine, busiest first
     std::vector<size_t> order(k2s_.size() / kK2Stat);
@@ -2459,6 +2504,282 @@ bool Engine::prefilter_only(const BatchInput& in, std::vector<std::vector<std::v
   return true;
 }
 
+// ---- wire packing of uploaded batches (wirepack.h)
+//
+// The link sets the step time of an uploaded batch, and source text is almost
+// all ASCII, so strips of a segment cross the link packed to 7 bits per byte
+// and are restored in the ring by tsg_wire_unpack before K1 reads them.  The
+// engine's packer threads claim strips from the front of the feeder's segment
+// (then of the next one) and pack them into the lane's pinned staging slots; the scan's feeder thread
+// owns the copy stream, keeps kWireCopiesAhead strip copies queued and, when
+// no packed strip is ready, claims a strip from the back of the segment and
+// sends it as it is from the caller's memory, so packing never makes the link
+// wait.  Unpack kernels run on the lane's third stream behind their copy's
+// event; up_done[slot] is recorded there once every copy of the segment and
+// every unpack is queued before it.
+constexpr size_t kWireCopiesAhead = 3;
+
+void wire_unpack_launch(const uint8_t* land, uint32_t tab_bytes, uint8_t* dst, uint32_t n, hipStream_t stream);
+
+struct WireFeed {
+  struct Seg { const uint8_t* src; uint64_t bytes; const uint64_t* offsets; uint32_t nfiles; };
+  std::vector<Seg> segs;               // in upload order; segment i goes to ring[i & 1]
+  Lane* ln = nullptr;
+  int device = 0;
+  uint64_t strip = 0;
+  bool force = false;                  // the feeder waits for the packers instead of sending raw strips
+  int npackers = 0;
+  bool timeline = false;
+  std::mutex mu;                       // guards everything below
+  std::condition_variable cv;
+  // per segment: strips [front, back) are unclaimed.  Packers take the
+  // front of the segment the feeder is on (feed_seg) and, once that one is
+  // claimed out, of the next, so the link does not wait for the first packed
+  // strips of a new segment (staging is not the ring: only the feeder, which
+  // launches the unpack, waits for the ring slot)
+  struct Span { uint32_t front = 0, back = 0; };
+  std::vector<Span> span;
+  size_t feed_seg = 0;
+  enum { kFree, kPacking, kReady, kFlying };
+  struct Slot { int state = kFree; size_t seg = 0; uint32_t strip = 0; uint64_t wire_len = 0; };
+  std::vector<Slot> slots;
+  std::deque<int> ready;
+  int nfree = 0;
+  bool stop = false, failed = false;
+  std::string err;
+  size_t segs_done = 0;                // driver: segments whose kernels have finished
+  size_t segs_recorded = 0;            // feeder: segments whose up_done is recorded
+  uint64_t wire_bytes = 0;
+  uint32_t packed = 0, raw = 0;
+  double pack_ms = 0;
+  std::thread feeder;
+  // feeder only: copies in flight (slot -1: a raw strip), unpacks in flight
+  struct Fly { hipEvent_t ev; int slot; };
+  std::deque<Fly> copies, unpacks;
+  uint32_t raw_i = 0;
+
+  int pack_seg() const {
+    for (size_t s = feed_seg; s < segs.size() && s <= feed_seg + 1; ++s)
+      if (span[s].front < span[s].back) return static_cast<int>(s);
+    return -1;
+  }
+  int ready_of(size_t seg) const {
+    for (size_t i = 0; i < ready.size(); ++i)
+      if (slots[ready[i]].seg == seg) return static_cast<int>(i);
+    return -1;
+  }
+  void pack_loop();
+  void feed_loop();
+  bool feed_segment(size_t si, std::string* err);
+  bool reap(std::string* err);
+};
+
+void WireFeed::pack_loop() {
+  std::unique_lock<std::mutex> lk(mu);
+  for (;;) {
+    cv.wait(lk, [&] { return stop || (nfree > 0 && pack_seg() >= 0); });
+    if (stop) return;
+    int id = 0;
+    while (slots[id].state != kFree) ++id;
+    slots[id].state = kPacking;
+    --nfree;
+    const size_t sgi = static_cast<size_t>(pack_seg());
+    const uint32_t s = span[sgi].front++;
+    const uint64_t o = static_cast<uint64_t>(s) * strip;
+    const uint8_t* p = segs[sgi].src + o;
+    const size_t n = static_cast<size_t>(std::min<uint64_t>(strip, segs[sgi].bytes - o));
+    lk.unlock();
+    auto t0 = std::chrono::steady_clock::now();
+    Lane::WireSlot& w = ln->wire[id];
+    const size_t tab = wire_table_bytes(n);
+    const size_t pl = wire_pack(p, n, w.h + tab, reinterpret_cast<uint32_t*>(w.h), kWireAuto);
+    const double ms = ms_since(t0);
+    lk.lock();
+    pack_ms += ms;
+    slots[id].seg = sgi;
+    slots[id].strip = s;
+    slots[id].wire_len = tab + pl;
+    slots[id].state = kReady;
+    ready.push_back(id);
+    cv.notify_all();
+  }
+}
+
+// Retires finished copies (waiting for the oldest while kWireCopiesAhead are
+// queued) and frees the staging slots whose unpack has completed.
+bool WireFeed::reap(std::string* err) {
+  while (!copies.empty()) {
+    const hipError_t r = copies.size() >= kWireCopiesAhead ? hipEventSynchronize(copies.front().ev)
+                                                           : hipEventQuery(copies.front().ev);
+    if (r == hipErrorNotReady) break;
+    HIP_OK(r);
+    copies.pop_front();
+  }
+  int freed = 0;
+  while (!unpacks.empty()) {
+    const hipError_t r = hipEventQuery(unpacks.front().ev);
+    if (r == hipErrorNotReady) break;
+    HIP_OK(r);
+    std::lock_guard<std::mutex> lk(mu);
+    slots[unpacks.front().slot].state = kFree;
+    ++nfree;
+    ++freed;
+    unpacks.pop_front();
+  }
+  if (freed) cv.notify_all();
+  return true;
+}
+
+bool WireFeed::feed_segment(size_t si, std::string* err) {
+  const Seg& sg = segs[si];
+  const int slot = static_cast<int>(si & 1);
+  HIP_OK(hipEventRecord(ln->up_begin[slot], ln->copy));
+  // (the slot's offsets staging was last read by the upload two segments
+  // back, complete since that segment's kernels waited on it)
+  std::memcpy(ln->h_off_pin[slot], sg.offsets, (sg.nfiles + 1) * sizeof(uint64_t));
+  HIP_OK(hipMemcpyAsync(ln->off_slot[slot], ln->h_off_pin[slot], (sg.nfiles + 1) * sizeof(uint64_t),
+                        hipMemcpyHostToDevice, ln->copy));
+  const uint32_t ns = static_cast<uint32_t>((sg.bytes + strip - 1) / strip);
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    feed_seg = si;
+  }
+  cv.notify_all();
+  uint64_t sent = 0;
+  uint32_t npacked = 0, nraw = 0;
+  for (uint32_t issued = 0; issued < ns;) {
+    if (!reap(err)) return false;
+    int id = -1;
+    uint32_t s = 0;
+    uint64_t wire_len = 0;
+    bool wait_gpu = false;
+    {
+      std::unique_lock<std::mutex> lk(mu);
+      if (stop) return true;             // (the scan is ending: feed_loop drains the streams)
+      const int ri = ready_of(si);
+      if (ri >= 0) {
+        id = ready[ri];
+        ready.erase(ready.begin() + ri);
+        s = slots[id].strip;
+        wire_len = slots[id].wire_len;
+        slots[id].state = kFlying;
+      } else if ((!force || npackers == 0) && span[si].front < span[si].back) {
+        s = --span[si].back;
+      } else if (copies.empty() && unpacks.empty()) {
+        // every strip left is with a packer
+        cv.wait(lk, [&] { return stop || ready_of(si) >= 0; });
+        continue;
+      } else {
+        wait_gpu = true;
+      }
+    }
+    if (wait_gpu) {
+      HIP_OK(hipEventSynchronize(!copies.empty() ? copies.front().ev : unpacks.front().ev));
+      continue;
+    }
+    const uint64_t o = static_cast<uint64_t>(s) * strip;
+    const size_t n = static_cast<size_t>(std::min<uint64_t>(strip, sg.bytes - o));
+    if (id >= 0 && wire_len >= n) {
+      // nothing gained (a strip of non-ASCII blocks): it goes as it is
+      std::lock_guard<std::mutex> lk(mu);
+      slots[id].state = kFree;
+      ++nfree;
+      id = -1;
+      cv.notify_all();
+    }
+    if (id < 0) {
+      HIP_OK(hipMemcpyAsync(ln->ring[slot] + o, sg.src + o, n, hipMemcpyHostToDevice, ln->copy));
+      hipEvent_t ev = ln->wire_raw_ev[raw_i++ & 3];
+      HIP_OK(hipEventRecord(ev, ln->copy));
+      copies.push_back({ev, -1});
+      sent += n;
+      ++nraw;
+    } else {
+      Lane::WireSlot& w = ln->wire[id];
+      HIP_OK(hipMemcpyAsync(w.d, w.h, wire_len, hipMemcpyHostToDevice, ln->copy));
+      HIP_OK(hipEventRecord(w.copied, ln->copy));
+      HIP_OK(hipStreamWaitEvent(ln->unpack, w.copied, 0));
+      wire_unpack_launch(w.d, static_cast<uint32_t>(wire_table_bytes(n)), ln->ring[slot] + o, static_cast<uint32_t>(n),
+                         ln->unpack);
+      HIP_OK(hipGetLastError());
+      HIP_OK(hipEventRecord(w.unpacked, ln->unpack));
+      copies.push_back({w.copied, id});
+      unpacks.push_back({w.unpacked, id});
+      sent += wire_len;
+      ++npacked;
+    }
+    ++issued;
+  }
+  HIP_OK(hipMemsetAsync(ln->ring[slot] + sg.bytes, 0, 64, ln->copy));   // K1 reads 16-B words past the end
+  HIP_OK(hipEventRecord(ln->wire_copies_done[slot], ln->copy));
+  HIP_OK(hipStreamWaitEvent(ln->unpack, ln->wire_copies_done[slot], 0));
+  HIP_OK(hipEventRecord(ln->up_done[slot], ln->unpack));
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    ++segs_recorded;
+    wire_bytes += sent;
+    packed += npacked;
+    raw += nraw;
+  }
+  cv.notify_all();
+  if (timeline) std::fprintf(stderr, "[tsg tl] seg %zu wire: %u strips packed, %u raw, %llu bytes sent\n", si, npacked,
+                             nraw, static_cast<unsigned long long>(sent));
+  return true;
+}
+
+void WireFeed::feed_loop() {
+  std::string e;
+  bool ok = true;
+  size_t si = 0;
+  try {
+    ok = hipSetDevice(device) == hipSuccess;
+    if (!ok) e = "hipSetDevice failed";
+    for (; ok && si < segs.size(); ++si) {
+      {
+        // ring[si & 1] was last read by the kernels of segment si - 2
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return stop || si < 2 || segs_done + 1 >= si; });
+        if (stop) break;
+      }
+      ok = feed_segment(si, &e);
+      std::lock_guard<std::mutex> lk(mu);
+      if (stop) break;
+    }
+  } catch (const std::exception& x) {
+    ok = false;
+    e = std::string("host exception in the upload feeder: ") + x.what();
+  }
+  if (!ok || si < segs.size()) {
+    // failed or stopped early: nothing of this scan stays queued on the
+    // feeder's streams, and no copy reads the caller's memory any more
+    hipStreamSynchronize(ln->copy);
+    hipStreamSynchronize(ln->unpack);
+  }
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    if (!ok) { failed = true; err = e; }
+    stop = true;
+  }
+  cv.notify_all();
+}
+
+void Engine::wire_packer_main() {
+  uint64_t seen = 0;
+  std::unique_lock<std::mutex> lk(wire_mu_);
+  for (;;) {
+    wire_cv_.wait(lk, [&] { return wire_stop_ || (wire_job_ && wire_gen_ != seen); });
+    if (wire_stop_) return;
+    seen = wire_gen_;
+    WireFeed* f = wire_job_;
+    ++wire_active_;
+    lk.unlock();
+    f->pack_loop();
+    lk.lock();
+    --wire_active_;
+    wire_cv_.notify_all();
+  }
+}
+
 bool Engine::feed_probe(const uint8_t* h_data, uint64_t bytes, double* ms, std::string* err) {
   DeviceTables& dt = *dev_[0];
   Lane* ln = acquire_lane(dt, err);
@@ -2974,6 +3295,12 @@ bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::
       (void)hipGetLastError();
   }
   const bool direct = h_dev != nullptr;
+  // wire packing: uploaded batches of at least four strips on one device,
+  // except the dense small-file batches whose bound is host confirmation
+  // (the packers would take its CPUs)
+  const bool wire_want = wire_mode_ != 0 && !resident && !direct && in.h_data && drivers.size() == 1 &&
+                         total >= 4 * wire_strip_ &&
+                         !(static_cast<double>(in.nfiles) * 1e9 > kDenseFilesPerGB * static_cast<double>(total));
   auto driver = [&](int di, std::string* e_out) -> bool {
     DeviceTables* dt = drivers[di];
     std::string e;
@@ -2981,6 +3308,8 @@ bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::
     auto tb = std::chrono::steady_clock::now();
     Lane* ln = nullptr;
     bool ok = false;
+    std::unique_ptr<WireFeed> wf;        // (set: this scan holds the engine's packers)
+    bool wire_held = false;
     // (a host exception -- bad_alloc of a plan or a copy-out -- ends this
     // driver like a HIP error: the queue is aborted and the call fails; it
     // must not escape the thread)
@@ -3005,6 +3334,7 @@ bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::
     }
     // upload of segment `si` into ring slot `slot` (copy stream)
     auto upload = [&](size_t si, int slot) -> bool {
+      if (wf) return true;               // (the feeder uploads the segments in order)
       const Segment& sg = segs[si];
       std::string* err = &e;
       HIP_OK(hipEventRecord(ln->up_begin[slot], ln->copy));
@@ -3033,6 +3363,63 @@ bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::
     size_t cur = ok ? pipe.next_segment() : segs.size();
     int slot = 0;
     if (ok && host_profile_) hipEventRecord(ln->anchor, resident ? ln->compute : ln->copy);
+    if (ok && wire_want) {
+      // one scan at a time has the packers; a concurrent one uploads as before
+      {
+        std::lock_guard<std::mutex> lk(wire_mu_);
+        if (!wire_busy_) wire_busy_ = wire_held = true;
+      }
+      if (wire_held) {
+        const int nt = threads_ > 0 ? threads_ : static_cast<int>(std::min(16u, std::max(1u, std::thread::hardware_concurrency())));
+        const int np = wire_threads_n_ >= 0 ? wire_threads_n_ : std::max(0, std::min(16, nt - 2));
+        const size_t nslots = np > 0 ? static_cast<size_t>(np) + kWireCopiesAhead : 0;
+        const size_t cap = wire_table_bytes(wire_strip_) + wire_bound(wire_strip_);
+        std::string* err = &e;
+        auto setup = [&]() -> bool {
+          if (!ln->unpack) HIP_OK(hipStreamCreateWithFlags(&ln->unpack, hipStreamNonBlocking));
+          const unsigned evf = hipEventBlockingSync | hipEventDisableTiming;
+          for (auto& ev : ln->wire_raw_ev) if (!ev) HIP_OK(hipEventCreateWithFlags(&ev, evf));
+          for (auto& ev : ln->wire_copies_done) if (!ev) HIP_OK(hipEventCreateWithFlags(&ev, evf));
+          if (ln->wire.size() < nslots || ln->wire_cap < cap) {
+            // (pinned staging of this size is far too slow to allocate per call: kept on the lane)
+            ln->free_wire();
+            ln->wire.resize(nslots);
+            ln->wire_cap = cap;
+            for (Lane::WireSlot& w : ln->wire) {
+              HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&w.h), cap, hipHostMallocDefault));
+              HIP_OK(hipMalloc(reinterpret_cast<void**>(&w.d), cap));
+              HIP_OK(hipEventCreateWithFlags(&w.copied, evf));
+              HIP_OK(hipEventCreateWithFlags(&w.unpacked, evf));
+            }
+          }
+          return true;
+        };
+        ok = setup();
+        if (ok) {
+          wf.reset(new WireFeed());
+          wf->ln = ln;
+          wf->device = dt->device;
+          wf->strip = wire_strip_;
+          wf->force = wire_mode_ == 2;
+          wf->npackers = np;
+          wf->timeline = host_profile_;
+          wf->slots.resize(nslots);
+          wf->nfree = static_cast<int>(nslots);
+          for (const Segment& sg : segs) {
+            wf->segs.push_back({sg.in.h_data, sg.bytes, sg.in.offsets, sg.in.nfiles});
+            wf->span.push_back({0, static_cast<uint32_t>((sg.bytes + wire_strip_ - 1) / wire_strip_)});
+          }
+          {
+            std::lock_guard<std::mutex> lk(wire_mu_);
+            while (static_cast<int>(wire_threads_.size()) < np) wire_threads_.emplace_back([this] { wire_packer_main(); });
+            wire_job_ = wf.get();
+            ++wire_gen_;
+          }
+          wire_cv_.notify_all();
+          wf->feeder = std::thread([f = wf.get()] { f->feed_loop(); });
+        }
+      }
+    }
     if (ok && cur < segs.size() && !resident && !direct) ok = upload(cur, slot);
     while (ok && cur < segs.size() && !q.aborted()) {
       // (resident data: the next segment is taken when this one is done, so
@@ -3066,6 +3453,12 @@ bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::
           HIP_OK(hipStreamWaitEvent(ln->compute, ln->up_done[slot], 0));
           return true;
         };
+        if (wf) {
+          // the feeder records up_done[slot] once the segment's last copy is queued
+          std::unique_lock<std::mutex> lk(wf->mu);
+          wf->cv.wait(lk, [&] { return wf->failed || wf->segs_recorded > cur; });
+          if (wf->failed) { ok = false; e = wf->err; break; }
+        }
         if (!(ok = wait_up())) break;
       }
       std::unique_ptr<Job> job(new Job());
@@ -3075,6 +3468,13 @@ bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::
       ok = run_segment(*dt, *ln, segs[cur], d_data, resident ? nullptr : ln->off_slot[slot], &sst, &job->out, &e,
                        &plan_pending, chain_p, /*defer_copy=*/true, direct ? &stage : nullptr);
       if (!ok) break;
+      if (wf) {
+        // this segment's ring slot may be written again
+        { std::lock_guard<std::mutex> lk(wf->mu); ++wf->segs_done; }
+        wf->cv.notify_all();
+      } else if (!resident) {
+        sst.wire_bytes += segs[cur].bytes;
+      }
       plan_pending();                    // (a rerun path may not have called it)
       if (host_profile_) {
         // GPU timeline of this segment from the scan's anchor event
@@ -3109,8 +3509,28 @@ bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::
       ok = false;
       e = "host exception in the device driver";
     }
+    if (wf) {
+      // the feeder and the packers stop and are parked before the call
+      // returns: nothing reads the caller's data after it
+      { std::lock_guard<std::mutex> lk(wf->mu); wf->stop = true; }
+      wf->cv.notify_all();
+      if (wf->feeder.joinable()) wf->feeder.join();
+    }
+    if (wire_held) {
+      std::unique_lock<std::mutex> lk(wire_mu_);
+      wire_job_ = nullptr;
+      wire_cv_.wait(lk, [&] { return wire_active_ == 0; });
+      wire_busy_ = false;
+    }
+    if (wf) {
+      if (host_profile_) std::fprintf(stderr, "[tsg tl] wire: %d packers busy %.3f ms in all\n", wf->npackers, wf->pack_ms);
+      dst.wire_bytes += wf->wire_bytes;
+      dst.packed_strips += wf->packed;
+      dst.raw_strips += wf->raw;
+      dst.pack_ms += wf->pack_ms;
+    }
     if (ln) {
-      if (!ok) { hipStreamSynchronize(ln->copy); hipStreamSynchronize(ln->compute); }
+      if (!ok) { hipStreamSynchronize(ln->copy); hipStreamSynchronize(ln->compute); if (ln->unpack) hipStreamSynchronize(ln->unpack); }
       ln->pool_idle = nullptr;                   // (the flag is this scan's)
       release_lane(*dt, ln);
     }
