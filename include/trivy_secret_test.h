@@ -92,6 +92,30 @@ int tsg_test_multi_driver_model(uint32_t ndevices, uint32_t nsegments, int32_t f
                                 uint32_t fail_mode, uint32_t seg_us, uint32_t confirm_us,
                                 tsg_model_pipeline_stats* out);
 
+/* The engine's segment planner (csrc/segments.h: plan_segments, the code
+ * Engine::scan cuts a batch with) on an offsets array alone: no engine, no
+ * device.  resident: the batch is device-resident at address `base` (used only
+ * for the 256-byte alignment of the pieces); with_paths 0: the batch has no
+ * paths (no lead files, as in the engine).  out[0, *nout) describes the
+ * segments (*nout is set even when it exceeds out_cap, which fails); rebased
+ * (may be NULL) receives each segment's nfiles + 1 rebased offsets, one
+ * segment after the other.  Tests only (tests/test_segments.py). */
+typedef struct {
+  uint32_t pieces;                 /* TSG_PIECES */
+  double first_piece, first_piece_few, last_piece;
+  uint64_t min_piece, segment, segment_min;
+  int32_t balanced;
+  double dense_files_per_gb;       /* the engine's kDenseFilesPerGB: 8000 */
+} tsg_segment_policy;
+typedef struct {
+  uint32_t f0, nfiles, lead;       /* first file of the batch; files with the lead; 1 = file 0 is a lead */
+  uint64_t b0, bytes;              /* first byte of f0 in the batch; bytes of the segment's own files */
+  uint64_t d_data;                 /* resident: the segment's device address (the lead's, if any) */
+} tsg_segment_info;
+int tsg_test_plan_segments(const uint64_t* offsets, uint32_t nfiles, int resident, uint64_t base, int with_paths,
+                           const tsg_segment_policy* pol, tsg_segment_info* out, uint32_t out_cap, uint32_t* nout,
+                           uint64_t* rebased, size_t rebased_cap);
+
 /* Test hook: the engine's next n segment runs fail before their first
  * launch (as a failed device allocation would), so a test can check that a
  * failed call leaves nothing behind on the engine's pooled lanes.  Never used

@@ -24,6 +24,17 @@ class TsgModelPipelineStats(ctypes.Structure):
                 ("wall_ms", ctypes.c_double), ("fail_to_return_ms", ctypes.c_double)]
 
 
+class TsgSegmentPolicy(ctypes.Structure):
+    _fields_ = [("pieces", ctypes.c_uint32), ("first_piece", ctypes.c_double), ("first_piece_few", ctypes.c_double),
+                ("last_piece", ctypes.c_double), ("min_piece", ctypes.c_uint64), ("segment", ctypes.c_uint64),
+                ("segment_min", ctypes.c_uint64), ("balanced", ctypes.c_int32), ("dense_files_per_gb", ctypes.c_double)]
+
+
+class TsgSegmentInfo(ctypes.Structure):
+    _fields_ = [("f0", ctypes.c_uint32), ("nfiles", ctypes.c_uint32), ("lead", ctypes.c_uint32),
+                ("b0", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("d_data", ctypes.c_uint64)]
+
+
 class TsgStats(ctypes.Structure):
     _fields_ = [("k1_ms", ctypes.c_double), ("k2_ms", ctypes.c_double), ("h2d_ms", ctypes.c_double),
                 ("d2h_ms", ctypes.c_double), ("host_ms", ctypes.c_double), ("total_ms", ctypes.c_double),
@@ -90,6 +101,10 @@ SIGNATURES = [
     ("tsg_test_multi_driver_model", ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint32,
                                                     ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                     ctypes.POINTER(TsgModelPipelineStats)]),
+    ("tsg_test_plan_segments", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64,
+                                               ctypes.c_int, ctypes.POINTER(TsgSegmentPolicy),
+                                               ctypes.POINTER(TsgSegmentInfo), ctypes.c_uint32,
+                                               ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p, ctypes.c_size_t]),
     ("tsg_test_engine_footprint", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
                                                   ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
     ("tsg_test_inject_segment_failures", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),

@@ -14,6 +14,7 @@
 
 #include "prefilter.h"
 #include "scanner.h"
+#include "segments.h"
 #include "wirepack.h"
 
 namespace tsg {
@@ -34,16 +35,6 @@ struct ScanStats {
   double pack_ms = 0;
 };
 
-struct BatchInput {
-  const uint8_t* h_data = nullptr;     // host copy (needed by the exact confirmer)
-  const void* d_data = nullptr;        // device copy; nullptr -> engine uploads h_data
-  const uint64_t* offsets = nullptr;   // nfiles + 1 byte offsets into data
-  uint32_t nfiles = 0;
-  const char* const* paths = nullptr;  // nfiles NUL-terminated paths (ScanArgs.FilePath)
-  const uint32_t* path_lens = nullptr; // optional explicit lengths
-  const uint8_t* binary = nullptr;     // optional ScanArgs.Binary flags
-};
-
 // A batch scan stage: results[i] = Scan(ScanArgs{paths[i], data[off[i]:off[i+1]],
 // binary[i]}) -- Engine::scan, or (tests only) the CPU model of its passes.
 using BatchScanFn = std::function<bool(const BatchInput& in, SecretVec* results, std::string* err)>;
@@ -55,6 +46,8 @@ struct CallCtx;
 struct K1Chain;
 struct StageIn;
 struct WireFeed;
+struct SegRun;
+struct SegmentDriver;
 
 // One engine = the compiled ruleset's device tables on every selected device.
 // scan() is reentrant: each call takes its own lane (HIP streams + scratch
@@ -78,8 +71,8 @@ class Engine {
                       ScanStats* stats, std::string* err);
 
   // Host-feed ceiling (no kernels): streams `bytes` of host memory through
-  // the first device's upload ring in segment_ pieces, as scan() does, and
-  // returns the wall time in ms.
+  // the first device's upload ring in pieces of the policy's segment bytes,
+  // as scan() does, and returns the wall time in ms.
   bool feed_probe(const uint8_t* h_data, uint64_t bytes, double* ms, std::string* err);
 
   // GPU-side CR strip of a device-resident batch on the first device
@@ -101,7 +94,6 @@ class Engine {
 
  private:
   Engine() = default;
-  struct Segment;
   // while_gpu (optional) runs once on the calling thread after the segment's
   // kernels are queued, before their readbacks are; chain (optional) orders
   // the K1 launches of several drivers of one device (K1Chain); defer_copy
@@ -111,6 +103,20 @@ class Engine {
   bool run_segment(DeviceTables& dt, Lane& ln, const Segment& sg, const void* d_data, const uint64_t* d_off_up,
                    ScanStats* st, GpuOut* out, std::string* err, const std::function<void()>* while_gpu = nullptr,
                    K1Chain* chain = nullptr, bool defer_copy = false, const StageIn* stage = nullptr);
+  // run_segment's phases (SegRun: what they share)
+  bool seg_geometry(SegRun& r, GpuOut* out, std::string* err);
+  bool seg_stage_offsets(SegRun& r, std::string* err);
+  bool seg_size_scratch(SegRun& r, std::string* err);
+  bool seg_prologue(SegRun& r, int attempt, std::string* err);
+  bool seg_k1_lds_limits(SegRun& r, std::string* err);
+  bool seg_launch_k1(SegRun& r, int attempt, std::string* err);
+  bool seg_launch_k2(SegRun& r, int a2, std::string* err);
+  bool seg_readback_wait(SegRun& r, int a2, std::string* err);
+  void seg_hand_off(SegRun& r, uint32_t ncands, uint32_t nover, bool defer_copy, GpuOut* out);
+  bool seg_write_traces(SegRun& r, std::string* err);   // (probe library)
+  bool fold_k2_stats(Lane& ln, std::string* err);
+  friend struct SegmentDriver;                           // a scan's device driver (engine.hip)
+  friend struct WireFeed;                                // takes and returns the engine's packers
   void plan_confirm(const Segment& sg, GpuOut* g) const;
   void confirm_segment(CallCtx& cc, const Segment& sg, GpuOut& g, Secret* results, uint64_t* nconf,
                        uint64_t* nfind, bool gpu_in_flight);
@@ -147,8 +153,6 @@ class Engine {
   // files 482 -> 570 (profiles/r5p_resident_variants.log).
   int resident_drivers_ = 2;
   int chain_k1_ = 1;                    // K1Chain: 0 = next K1 after this K2, 1 = after this K1, 2 = no wait (TSG_CHAIN_K1)
-  uint32_t k1_reserve_cus_ = 0;         // K1Chain pieces: CUs left out of K1's grid for the previous piece's K2 / readback (TSG_K1_RESERVE_CUS)
-  bool readback_dma_ = false;           // K1Chain pieces read back by DMA copies instead of tsg_readback (TSG_READBACK_DMA)
   bool file_index_ = true;              // K1 range starts' files from a per-64-KiB index (TSG_K1_FILE_INDEX)
   // Wire packing of uploaded batches (wirepack.h; TSG_WIRE_PACK 0 = off, 1 =
   // packers race the link, force = every strip waits for a packer).  The
@@ -187,24 +191,7 @@ class Engine {
   std::atomic<uint32_t> inject_fail_{0};
   std::mutex k2s_mu_;
   std::vector<unsigned long long> k2s_;  // 4 per rule: hits, past the keyword gate, verify starts, bytes walked
-  // resident data: pipeline pieces (TSG_PIECES; r3za config 2: 4 pieces,
-  // first 10%: 1286 GB/s, 2 at 70/30: 919), the first piece's share
-  // (TSG_FIRST_PIECE) and a short last piece's (TSG_LAST_PIECE, 0: none; used
-  // from 5 pieces on).  Round 5, K2 beside the next K1 (K1Chain): 5 pieces
-  // with an 8% last piece 1921 GB/s vs 4 pieces 1796 on config 2 -- the last
-  // piece's K2 and host confirmation are the step's tail; 1 GB of config-1
-  // files gains nothing from more pieces (profiles/r5t_resident_pieces.log)
-  uint32_t pieces_ = 5;
-  double first_piece_ = 0.1;
-  double first_piece_few_ = 0.2;        // the first piece's share when a batch makes 3 pieces (TSG_FIRST_PIECE_FEW)
-  double last_piece_ = 0.08;
-  uint64_t min_piece_ = 256ull << 20;   // resident data: smaller batches run as one piece (TSG_MIN_PIECE_BYTES)
-  uint64_t segment_min_ = 64ull << 20;   // uploaded data: smallest segment of the geometric tail (TSG_SEGMENT_MIN; r3s: 128 MB 51.5 vs 256 MB 48.8 GB/s on config 1; r4p: 64 MB 53.2 vs 128 MB 52.5)
-  bool balanced_ = true;                // uploaded large-file data: equal segments of <= segment_ (TSG_SEGMENT_BALANCED)
-  uint64_t segment_tail_ = 0;           // uploaded data: a short last segment (TSG_SEGMENT_TAIL; 0 = none: the
-                                        // rest after the full segments is one launch, K1 keeps its large-launch rate)
-  uint64_t segment_ = 4ull << 30;       // uploaded data: bytes per pipeline segment (TSG_SEGMENT_BYTES);
-                                        // 1 GB = one full K1 round (256 CUs x 1024 lanes x 4 KiB chunks)
+  SegmentPolicy seg_;                   // where a batch is cut (segments.h: TSG_PIECES, TSG_SEGMENT_BYTES, ...)
 };
 
 int device_count();

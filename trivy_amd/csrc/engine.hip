@@ -1357,25 +1357,38 @@ const void* k1_kernel(int abl, bool compressed) {
 // ==== host side: K1's build hash (bench.py k1_build) ends here -- a
 // committed traffic measurement applies to that code
 
+// A device buffer and its capacity in elements, freed with its owner.
 template <typename T>
-bool dev_upload(const std::vector<T>& v, T** out, std::string* err) {
-  size_t n = std::max<size_t>(v.size(), 1) * sizeof(T);
-  HIP_OK(hipMalloc(reinterpret_cast<void**>(out), n + 16));
-  HIP_OK(hipMemset(*out, 0, n + 16));
-  if (!v.empty()) HIP_OK(hipMemcpy(*out, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  return true;
-}
-
-template <typename T>
-bool ensure(T** p, size_t* cap, size_t n, std::string* err) {
-  if (*cap >= n && *p) return true;
-  if (*p) HIP_OK(hipFree(*p));
-  *p = nullptr;
-  size_t want = std::max<size_t>(n, 1);
-  HIP_OK(hipMalloc(reinterpret_cast<void**>(p), want * sizeof(T) + 64));
-  *cap = want;
-  return true;
-}
+struct DevBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  // room for n elements (contents are lost when it grows)
+  bool ensure(size_t n, std::string* err) {
+    if (cap >= n && p) return true;
+    if (p) HIP_OK(hipFree(p));
+    p = nullptr;
+    cap = 0;
+    const size_t want = std::max<size_t>(n, 1);
+    HIP_OK(hipMalloc(reinterpret_cast<void**>(&p), want * sizeof(T) + 64));
+    cap = want;
+    return true;
+  }
+  // a rule table: v's bytes, zero padded by 16
+  template <typename U>
+  bool upload(const std::vector<U>& v, std::string* err) {
+    const size_t n = std::max<size_t>(v.size(), 1) * sizeof(U);
+    HIP_OK(hipMalloc(reinterpret_cast<void**>(&p), n + 16));
+    cap = n / sizeof(T);
+    HIP_OK(hipMemset(p, 0, n + 16));
+    if (!v.empty()) HIP_OK(hipMemcpy(p, v.data(), v.size() * sizeof(U), hipMemcpyHostToDevice));
+    return true;
+  }
+};
 
 // Default K1 chunk for a launch of `bytes` on `lanes` lanes (CUs x 1024).  K1
 // walks ranges of 1-4 chunks per lane (guided schedule; 1-8 with top8): its
@@ -1414,10 +1427,10 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
 
 // Device tables of one scan DFA group (one K1 launch per group).
 struct K1Group {
-  uint16_t* next = nullptr;    // pre-multiplied uint16 row offsets, row stride `stride`
-  uint8_t* cls = nullptr;      // byte -> class * 2
-  OutMeta* meta = nullptr;
-  uint32_t* list = nullptr;
+  DevBuf<uint16_t> next;       // pre-multiplied uint16 row offsets, row stride `stride`
+  DevBuf<uint8_t> cls;         // byte -> class * 2
+  DevBuf<OutMeta> meta;
+  DevBuf<uint32_t> list;
   uint32_t nmeta = 0, nlist = 0, table_words16 = 0, stride = 0, ostride = 0, nclasses = 0, first_out = 0;
   uint32_t kw_base = 0, warm_lines = 0, warm_lines64 = 0;
   size_t meta_bytes = 0;
@@ -1430,10 +1443,10 @@ struct DeviceTables {
   int device = 0;
   int sms = 256;
   std::vector<K1Group> k1g;
-  K2Anchor* anchors = nullptr;                 // K2's per-anchor records
-  uint32_t* rule_kw = nullptr;
-  uint16_t* v_next = nullptr;
-  uint8_t* v_cls = nullptr;
+  DevBuf<K2Anchor> anchors;                    // K2's per-anchor records
+  DevBuf<uint32_t> rule_kw;
+  DevBuf<uint16_t> v_next;
+  DevBuf<uint8_t> v_cls;
   uint32_t kw_words = 1;
   std::mutex mu;                               // guards the lane pool and lds_set
   std::vector<std::pair<const void*, int>> lds_set;   // K1 builds whose dynamic-LDS limit is set (per device)
@@ -1442,28 +1455,39 @@ struct DeviceTables {
   ~DeviceTables();
 };
 
-// One in-flight call's resources on one device: its own streams (compute +
-// copy), timing events, the two-slot upload ring and every per-batch scratch
-// buffer, so concurrent calls never share mutable GPU state.
+// Pinned host memory, freed with its owner.
 struct PinnedBuf {
   void* p = nullptr;     // host address
   void* d = nullptr;     // the same memory as the device sees it
-  size_t cap = 0;
+  size_t cap = 0;        // bytes
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf&) = delete;
+  PinnedBuf& operator=(const PinnedBuf&) = delete;
+  ~PinnedBuf() { if (p) (void)hipHostFree(p); }
   template <typename T> T* as() const { return static_cast<T*>(p); }
+  // room for `bytes` (and `slack` more, not counted in cap), allocated with
+  // `flags`; contents are lost when it grows
+  bool ensure(size_t bytes, unsigned flags, std::string* err, size_t slack = 0) {
+    if (p && cap >= bytes) return true;
+    if (p) HIP_OK(hipHostFree(p));
+    p = d = nullptr;
+    cap = 0;
+    HIP_OK(hipHostMalloc(&p, std::max<size_t>(bytes + slack, 1), flags));
+    HIP_OK(hipHostGetDevicePointer(&d, p, 0));
+    cap = bytes;
+    return true;
+  }
+  // host-mapped, coherent (fine-grained) memory for tsg_readback: grown with 25 % head-room
+  bool ensure_readback(size_t bytes, std::string* err) {
+    if (p && cap >= bytes) return true;
+    const size_t want = (std::max<size_t>(bytes + bytes / 4, 256) + 63) & ~size_t(63);
+    return ensure(want, hipHostMallocMapped | hipHostMallocCoherent, err, 64);
+  }
+  // a segment's offsets on their way to the device: exact size, plain pinned
+  bool ensure_offsets(size_t nfiles, std::string* err) {
+    return ensure((nfiles + 1) * sizeof(uint64_t), hipHostMallocDefault, err);
+  }
 };
-
-// host-mapped, coherent (fine-grained) pinned memory for tsg_readback
-bool ensure_pinned(PinnedBuf* b, size_t bytes, std::string* err) {
-  if (b->p && b->cap >= bytes) return true;
-  if (b->p) HIP_OK(hipHostFree(b->p));
-  b->p = b->d = nullptr;
-  b->cap = 0;
-  const size_t want = (std::max<size_t>(bytes + bytes / 4, 256) + 63) & ~size_t(63);
-  HIP_OK(hipHostMalloc(&b->p, want + 64, hipHostMallocMapped | hipHostMallocCoherent));
-  HIP_OK(hipHostGetDevicePointer(&b->d, b->p, 0));
-  b->cap = want;
-  return true;
-}
 
 // Readbacks of one segment: dwords of device buffers into host-mapped
 // pinned buffers, queued together as one tsg_readback launch on stream s
@@ -1517,55 +1541,74 @@ struct StageIn {
 constexpr uint64_t kDirectStageBytes = 1u << 20;     // batches up to this size (and pinned) are staged by the prologue
 constexpr int kWirePackDefault = 1;            // TSG_WIRE_PACK unset: 1 = packers race the link (wirepack.h)
 
-struct Lane {
-  int device = 0;
+// One in-flight call's resources on one device: its own streams (compute +
+// copy), timing events, the two-slot upload ring and every per-batch scratch
+// buffer, so concurrent calls never share mutable GPU state.
+//
+// The streams and events are a base of Lane, so they are destroyed after the
+// lane's buffers (members) are freed, which is after ~Lane has synchronized
+// the streams.
+struct LaneStreams {
   hipStream_t compute = nullptr, copy = nullptr;
   hipEvent_t ev[4] = {};                        // K1 start/end, K2 start/end (compute stream)
   hipEvent_t ev_sync = nullptr;                 // blocking-sync event (K1Chain drivers)
-  const std::atomic<bool>* pool_idle = nullptr; // set by a scan's driver: its confirm pool has no work
   hipEvent_t up_begin[2] = {}, up_done[2] = {}; // upload ring slot: H2D start / done (copy stream)
   hipEvent_t anchor = nullptr;                   // TSG_HOST_PROFILE: start of a scan() on the copy stream
+  // wire packing (WireFeed): the stream the unpack kernels run on; events of
+  // the raw strip copies in flight and of a segment's last copy
+  hipStream_t unpack = nullptr;
+  hipEvent_t wire_raw_ev[4] = {};
+  hipEvent_t wire_copies_done[2] = {};
+  ~LaneStreams() {
+    for (hipEvent_t* e : {&ev[0], &ev[1], &ev[2], &ev[3], &ev_sync, &up_begin[0], &up_begin[1], &up_done[0], &up_done[1],
+                          &anchor, &wire_raw_ev[0], &wire_raw_ev[1], &wire_raw_ev[2], &wire_raw_ev[3],
+                          &wire_copies_done[0], &wire_copies_done[1]})
+      if (*e) (void)hipEventDestroy(*e);
+    for (hipStream_t st : {unpack, compute, copy}) if (st) (void)hipStreamDestroy(st);
+  }
+};
+
+struct Lane : LaneStreams {
+  int device = 0;
+  const std::atomic<bool>* pool_idle = nullptr; // set by a scan's driver: its confirm pool has no work
   // wire packing (WireFeed): pinned staging slots the packers fill, each with
-  // a device landing twin; the stream the unpack kernels run on; events of the
-  // raw strip copies in flight and of a segment's last copy
+  // a device landing twin and the events of its copy and unpack; a slot's
+  // four parts live and die together (free_wire)
   struct WireSlot {
     uint8_t* h = nullptr; uint8_t* d = nullptr;
     hipEvent_t copied = nullptr, unpacked = nullptr;
   };
   std::vector<WireSlot> wire;
   size_t wire_cap = 0;
-  hipStream_t unpack = nullptr;
-  hipEvent_t wire_raw_ev[4] = {};
-  hipEvent_t wire_copies_done[2] = {};
-  uint8_t* ring[2] = {nullptr, nullptr};
-  size_t ring_cap[2] = {0, 0};
-  uint64_t* d_off = nullptr; size_t d_off_cap = 0;
+  DevBuf<uint8_t> ring[2];
+  DevBuf<uint64_t> d_off;
   // uploaded data: the segment's offsets travel on the copy stream with its
   // bytes, from pinned staging (a pageable copy of >~64 KB on the compute
   // stream is staged through the copy engine and queues behind the next
   // segment's upload: measured, config 1's first K1 waited 8.8 ms)
-  uint64_t* off_slot[2] = {nullptr, nullptr}; size_t off_slot_cap[2] = {0, 0};
-  uint64_t* h_off_pin[2] = {nullptr, nullptr}; size_t h_off_pin_cap[2] = {0, 0};
+  DevBuf<uint64_t> off_slot[2];
+  PinnedBuf h_off_pin[2];
   // readbacks land in pinned memory (a pageable D2H is staged through a copy
   // engine and at times waited behind the next segment's upload: r3q/r3u
   // config 2, up to 22 ms between K2 done and the results on the host)
   PinnedBuf rb_bh, rb_c2, rb_cands, rb_ff, rb_nl;
-  uint32_t* d_kw = nullptr; size_t d_kw_cap = 0;
-  unsigned long long* d_hits = nullptr; size_t d_hits_cap = 0;
-  unsigned long long* d_over = nullptr; size_t d_over_cap = 0;   // hits past a full region (any workgroup)
-  uint32_t* d_bh = nullptr; size_t d_bh_cap = 0;    // hits written per K1 workgroup (its region of d_hits)
-  CandDev* d_cands = nullptr; size_t d_cands_cap = 0;
-  uint16_t* d_nl = nullptr; size_t d_nl_cap = 0;   // '\n' per K1 chunk (chunk <= 32 KiB)
-  uint32_t* d_cf = nullptr; size_t d_cf_cap = 0;   // per K1 chunk: a file at or before its first byte (K2's file lookup)
-  uint32_t* d_ff = nullptr; size_t d_ff_cap = 0;
-  uint32_t* d_ob = nullptr; size_t d_ob_cap = 0;    // K1 v3 deferred-output slots (kOutSlots per thread)
-  uint32_t* d_fidx = nullptr; size_t d_fidx_cap = 0;   // K1's file index (tsg_file_index): one entry per 64 KiB
-  unsigned long long* d_k2s = nullptr;              // TSG_K2_STATS: per-rule K2 counters (4 per rule)
-  unsigned int* d_cnt = nullptr;
-  uint8_t* d_cr = nullptr; size_t d_cr_cap = 0;     // CR strip scratch (crstrip.hip)
+  DevBuf<uint32_t> d_kw;
+  DevBuf<unsigned long long> d_hits;
+  DevBuf<unsigned long long> d_over;   // hits past a full region (any workgroup)
+  DevBuf<uint32_t> d_bh;               // hits written per K1 workgroup (its region of d_hits)
+  DevBuf<CandDev> d_cands;
+  DevBuf<uint16_t> d_nl;               // '\n' per K1 chunk (chunk <= 32 KiB)
+  DevBuf<uint32_t> d_cf;               // per K1 chunk: a file at or before its first byte (K2's file lookup)
+  DevBuf<uint32_t> d_ff;
+  DevBuf<uint32_t> d_ob;               // K1 v3 deferred-output slots (kOutSlots per thread)
+  DevBuf<uint32_t> d_fidx;             // K1's file index (tsg_file_index): one entry per 64 KiB
+  DevBuf<unsigned long long> d_k2s;    // TSG_K2_STATS: per-rule K2 counters (4 per rule)
+  DevBuf<unsigned int> d_cnt;
+  DevBuf<uint8_t> d_cr;                // CR strip scratch (crstrip.hip)
   size_t hit_cap = 1 << 20, cand_cap = 1 << 18, over_cap = 1 << 18;
   double k2_maxr_per_byte = 0;                       // K2 grid of the next segment: the last one's fullest region
   uint64_t k2_over_est = 0;                          // per byte, and its overflow hit count
+  bool ensure_wire(size_t nslots, size_t cap, std::string* err);
   void free_wire();
   ~Lane();
 };
@@ -1616,32 +1659,9 @@ struct CallCtx {
   }
 };
 
-// A self-contained sub-batch: files [f0, f0 + in.nfiles) of the call's
-// batch, offsets rebased to 0, data pointers advanced to its first byte.
-struct Engine::Segment {
-  BatchInput in;
-  std::vector<uint64_t> off;
-  uint32_t f0 = 0;
-  uint64_t b0 = 0, bytes = 0;
-  // resident pieces: file 0 of `in` is a lead of the bytes between the
-  // 256-byte boundary below the piece's first file and that file (the tail of
-  // the previous piece), so K1's lines are aligned as on the pinned path; its
-  // results are dropped.  lead_* hold the shifted path / length / binary arrays.
-  uint32_t lead = 0;
-  std::vector<const char*> lead_paths;
-  std::vector<uint32_t> lead_lens;
-  std::vector<uint8_t> lead_bin;
-};
-
 DeviceTables::~DeviceTables() {
   hipSetDevice(device);
-  lanes.clear();
-  void* ps[] = {anchors, rule_kw, v_next, v_cls};
-  for (void* p : ps) if (p) hipFree(p);
-  for (K1Group& g : k1g) {
-    void* gs[] = {g.next, g.cls, g.meta, g.list};
-    for (void* p : gs) if (p) hipFree(p);
-  }
+  lanes.clear();                                // (before the tables: the member order would free them after)
 }
 
 void Lane::free_wire() {
@@ -1655,28 +1675,34 @@ void Lane::free_wire() {
   wire_cap = 0;
 }
 
+// The wire feed's stream, events and `nslots` staging slots of `cap` bytes
+// (pinned staging of this size is far too slow to allocate per call: kept on
+// the lane).
+bool Lane::ensure_wire(size_t nslots, size_t cap, std::string* err) {
+  if (!unpack) HIP_OK(hipStreamCreateWithFlags(&unpack, hipStreamNonBlocking));
+  const unsigned evf = hipEventBlockingSync | hipEventDisableTiming;
+  for (auto& e : wire_raw_ev) if (!e) HIP_OK(hipEventCreateWithFlags(&e, evf));
+  for (auto& e : wire_copies_done) if (!e) HIP_OK(hipEventCreateWithFlags(&e, evf));
+  if (wire.size() >= nslots && wire_cap >= cap) return true;
+  free_wire();
+  wire.resize(nslots);
+  wire_cap = cap;
+  for (WireSlot& w : wire) {
+    HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&w.h), cap, hipHostMallocDefault));
+    HIP_OK(hipMalloc(reinterpret_cast<void**>(&w.d), cap));
+    HIP_OK(hipEventCreateWithFlags(&w.copied, evf));
+    HIP_OK(hipEventCreateWithFlags(&w.unpacked, evf));
+  }
+  return true;
+}
+
 Lane::~Lane() {
   hipSetDevice(device);
   if (compute) hipStreamSynchronize(compute);
   if (copy) hipStreamSynchronize(copy);
   if (unpack) hipStreamSynchronize(unpack);
   free_wire();
-  for (auto& e : wire_raw_ev) if (e) hipEventDestroy(e);
-  for (auto& e : wire_copies_done) if (e) hipEventDestroy(e);
-  if (unpack) hipStreamDestroy(unpack);
-  for (uint64_t* h : h_off_pin) if (h) hipHostFree(h);
-  for (PinnedBuf* b : {&rb_bh, &rb_c2, &rb_cands, &rb_ff, &rb_nl}) if (b->p) hipHostFree(b->p);
-  void* ps[] = {ring[0], ring[1], off_slot[0], off_slot[1], d_off, d_kw, d_hits, d_over, d_bh, d_cands, d_nl, d_cf, d_ff, d_ob, d_cnt, d_k2s, d_cr, d_fidx};
-  for (void* p : ps) if (p) hipFree(p);
-  for (auto& e : ev) if (e) hipEventDestroy(e);
-  if (ev_sync) hipEventDestroy(ev_sync);
-  if (anchor) hipEventDestroy(anchor);
-  for (int i = 0; i < 2; ++i) {
-    if (up_begin[i]) hipEventDestroy(up_begin[i]);
-    if (up_done[i]) hipEventDestroy(up_done[i]);
-  }
-  if (compute) hipStreamDestroy(compute);
-  if (copy) hipStreamDestroy(copy);
+  // (then the buffers, then ~LaneStreams)
 }
 
 int device_count() {
@@ -1692,30 +1718,18 @@ bool readback_probe(uint32_t nwords, uint32_t count, uint32_t per_count, uint32_
   const size_t n4 = (static_cast<size_t>(nwords) + 3) & ~size_t(3);   // the kernel moves 16-byte granules
   std::vector<uint32_t> h(n4 + 4);
   for (size_t i = 0; i < h.size(); ++i) h[i] = static_cast<uint32_t>(i + 1);
-  uint32_t* d_src = nullptr;
-  uint32_t* d_cnt = nullptr;
+  DevBuf<uint32_t> d_src, d_cnt;
   PinnedBuf dst;
-  bool ok = false;
-  std::string e2;
-  do {
-    if (hipMalloc(&d_src, h.size() * 4) != hipSuccess || hipMalloc(&d_cnt, 4) != hipSuccess) { e2 = "hipMalloc"; break; }
-    if (hipMemcpy(d_src, h.data(), h.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_cnt, &count, 4, hipMemcpyHostToDevice) != hipSuccess) { e2 = "hipMemcpy"; break; }
-    if (!ensure_pinned(&dst, h.size() * 4, &e2)) break;
-    std::memset(dst.p, 0, dst.cap);
-    if (!readback(d_src, dst, nwords, d_cnt, per_count, nullptr, &e2)) break;
-    if (hipDeviceSynchronize() != hipSuccess) { e2 = "hipDeviceSynchronize"; break; }
-    const uint32_t* got = dst.as<const uint32_t>();
-    uint32_t n = 0;
-    while (n < n4 && got[n] == n + 1) ++n;
-    *copied = n;
-    ok = true;
-  } while (false);
-  if (d_src) hipFree(d_src);
-  if (d_cnt) hipFree(d_cnt);
-  if (dst.p) hipHostFree(dst.p);
-  if (!ok) *err = e2;
-  return ok;
+  if (!d_src.upload(h, err) || !d_cnt.upload(std::vector<uint32_t>{count}, err)) return false;
+  if (!dst.ensure_readback(h.size() * 4, err)) return false;
+  std::memset(dst.p, 0, dst.cap);
+  if (!readback(d_src.p, dst, nwords, d_cnt.p, per_count, nullptr, err)) return false;
+  HIP_OK(hipDeviceSynchronize());
+  const uint32_t* got = dst.as<const uint32_t>();
+  uint32_t n = 0;
+  while (n < n4 && got[n] == n + 1) ++n;
+  *copied = n;
+  return true;
 }
 
 namespace {
@@ -1749,12 +1763,12 @@ bool build_tables(const Prefilter& pf, DeviceTables* dt, std::string* err) {
     std::vector<OutMeta> meta;
     for (const auto& o : c.outs) meta.push_back(OutMeta{o.kw0, o.kw1, o.list_begin, o.list_count});
     std::vector<uint8_t> cls(c.cls4, c.cls4 + 256);
-    if (!dev_upload(img, reinterpret_cast<uint32_t**>(&g.next), err) || !dev_upload(cls, &g.cls, err) ||
-        !dev_upload(meta, &g.meta, err) || !dev_upload(c.out_list, &g.list, err)) {
+    if (!g.next.upload(img, err) || !g.cls.upload(cls, err) || !g.meta.upload(meta, err) ||
+        !g.list.upload(c.out_list, err)) {
       return false;
     }
     dt->kw_words = std::max<uint32_t>(dt->kw_words, 4);
-    dt->k1g.push_back(g);
+    dt->k1g.push_back(std::move(g));
   }
   for (const ScanDfa& sd : pf.groups) {
     if (pf.compressed.ok) break;
@@ -1824,12 +1838,11 @@ bool build_tables(const Prefilter& pf, DeviceTables* dt, std::string* err) {
     // K1's class map holds class * 2 (see k1_step)
     std::vector<uint8_t> cls(256);
     for (int b = 0; b < 256; ++b) cls[b] = static_cast<uint8_t>(sd.t.byte_class[b] * 2);
-    if (!dev_upload(sn, &g.next, err) || !dev_upload(cls, &g.cls, err) || !dev_upload(meta, &g.meta, err) ||
-        !dev_upload(olist, &g.list, err)) {
+    if (!g.next.upload(sn, err) || !g.cls.upload(cls, err) || !g.meta.upload(meta, err) || !g.list.upload(olist, err)) {
       return false;
     }
     dt->kw_words = std::max<uint32_t>(dt->kw_words, g.kw_base / 32 + 4);   // a group's masks span 4 words from kw_base
-    dt->k1g.push_back(g);
+    dt->k1g.push_back(std::move(g));
   }
   // K2: the verify DFAs' transitions with the accept flag in bit 15, and
   // one record per anchor (its rule's fields and DFA offsets inline)
@@ -1866,8 +1879,8 @@ bool build_tables(const Prefilter& pf, DeviceTables* dt, std::string* err) {
     k.flags = flags;
     an.push_back(k);
   }
-  return dev_upload(an, &dt->anchors, err) && dev_upload(pf.rule_kw, &dt->rule_kw, err) &&
-         dev_upload(vn, &dt->v_next, err) && dev_upload(vc, &dt->v_cls, err);
+  return dt->anchors.upload(an, err) && dt->rule_kw.upload(pf.rule_kw, err) && dt->v_next.upload(vn, err) &&
+         dt->v_cls.upload(vc, err);
 }
 
 // Device of a device pointer (-1: not a device allocation).
@@ -1876,6 +1889,35 @@ int device_of(const void* p) {
   if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return -1; }
   if (a.type != hipMemoryTypeDevice) return -1;
   return a.device;
+}
+
+// A TSG_* knob read at Engine::create: a value outside [lo, hi] is ignored.
+template <typename T>
+void env_int(const char* name, long long lo, long long hi, T* out) {
+  const char* c = std::getenv(name);
+  if (!c) return;
+  const long long v = std::atoll(c);
+  if (v >= lo && v <= hi) *out = static_cast<T>(v);
+}
+
+// The same for a share in (lo, hi), or [lo, hi) with lo_in.
+void env_double(const char* name, double lo, bool lo_in, double hi, double* out) {
+  const char* c = std::getenv(name);
+  if (!c) return;
+  const double v = std::atof(c);
+  if ((lo_in ? v >= lo : v > lo) && v < hi) *out = v;
+}
+
+// The device's view of h if it is pinned host memory, else nullptr.
+const uint8_t* pinned_device_view(const uint8_t* h) {
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, h) != hipSuccess || a.type != hipMemoryTypeHost || !a.devicePointer) {
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  // (the attributes may describe the allocation's base: offset the device view likewise)
+  const uint8_t* hp = a.hostPointer ? static_cast<const uint8_t*>(a.hostPointer) : h;
+  return static_cast<const uint8_t*>(a.devicePointer) + (h - hp);
 }
 
 void add_stats(ScanStats* a, const ScanStats& s) {
@@ -1901,47 +1943,22 @@ std::unique_ptr<Engine> Engine::create(std::shared_ptr<const Ruleset> rs, const 
   e->rs_ = std::move(rs);
   e->devices_ = devices;
   if (!build_prefilter(*e->rs_, &e->pf_, err)) return nullptr;
-  if (const char* c = std::getenv("TSG_PIECES")) {
-    const long v = std::atol(c);
-    if (v >= 1 && v <= 64) e->pieces_ = static_cast<uint32_t>(v);
-  }
-  if (const char* c = std::getenv("TSG_FIRST_PIECE")) {
-    const double v = std::atof(c);
-    if (v > 0.0 && v < 1.0) e->first_piece_ = v;
-  }
-  if (const char* c = std::getenv("TSG_FIRST_PIECE_FEW")) {
-    const double v = std::atof(c);
-    if (v > 0.0 && v < 1.0) e->first_piece_few_ = v;
-  }
-  if (const char* c = std::getenv("TSG_LAST_PIECE")) {
-    const double v = std::atof(c);
-    if (v >= 0.0 && v < 0.5) e->last_piece_ = v;
-  }
-  if (const char* c = std::getenv("TSG_MIN_PIECE_BYTES")) {
-    const long long v = std::atoll(c);
-    if (v >= 1) e->min_piece_ = static_cast<uint64_t>(v);
-  }
-  if (const char* c = std::getenv("TSG_SEGMENT_BYTES")) {
-    const long long v = std::atoll(c);
-    if (v >= 4096) e->segment_ = static_cast<uint64_t>(v);
-  }
-  if (const char* c = std::getenv("TSG_SEGMENT_MIN")) {
-    const long long v = std::atoll(c);
-    if (v >= 4096) e->segment_min_ = static_cast<uint64_t>(v);
-  }
-  if (const char* c = std::getenv("TSG_SEGMENT_BALANCED")) e->balanced_ = std::atoi(c) != 0;
-  if (const char* c = std::getenv("TSG_SEGMENT_TAIL")) {
-    const long long v = std::atoll(c);
-    if (v >= 0) e->segment_tail_ = static_cast<uint64_t>(v);
-  }
+  SegmentPolicy& sp = e->seg_;
+  sp.dense_files_per_gb = kDenseFilesPerGB;
+  env_int("TSG_PIECES", 1, 64, &sp.pieces);
+  env_double("TSG_FIRST_PIECE", 0.0, false, 1.0, &sp.first_piece);
+  env_double("TSG_FIRST_PIECE_FEW", 0.0, false, 1.0, &sp.first_piece_few);
+  env_double("TSG_LAST_PIECE", 0.0, true, 0.5, &sp.last_piece);
+  env_int("TSG_MIN_PIECE_BYTES", 1, INT64_MAX, &sp.min_piece);
+  env_int("TSG_SEGMENT_BYTES", 4096, INT64_MAX, &sp.segment);
+  env_int("TSG_SEGMENT_MIN", 4096, INT64_MAX, &sp.segment_min);
+  if (const char* c = std::getenv("TSG_SEGMENT_BALANCED")) sp.balanced = std::atoi(c) != 0;
   if (const char* c = std::getenv("TSG_K1_ABL")) e->k1_abl_ = std::atoi(c);   // K1 measurement builds (kAbl bits)
   if (const char* c = std::getenv("TSG_K2_STATS")) e->k2_stats_ = std::atoi(c) != 0;
   if (const char* c = std::getenv("TSG_K2_ABL")) e->k2_abl_ = std::atoi(c) & (kK2Trace | kK2NoWalk);   // probe library builds
   if (const char* c = std::getenv("TSG_RESIDENT_DRIVERS")) e->resident_drivers_ = std::max(1, std::atoi(c));
   if (const char* c = std::getenv("TSG_CHAIN_K1")) e->chain_k1_ = std::max(0, std::min(2, std::atoi(c)));
-  if (const char* c = std::getenv("TSG_READBACK_DMA")) e->readback_dma_ = std::atoi(c) != 0;
   if (const char* c = std::getenv("TSG_K1_FILE_INDEX")) e->file_index_ = std::atoi(c) != 0;
-  if (const char* c = std::getenv("TSG_K1_RESERVE_CUS")) e->k1_reserve_cus_ = static_cast<uint32_t>(std::max(0, std::min(64, std::atoi(c))));
   if (const char* c = std::getenv("TSG_CONFIRM_PREFETCH")) e->confirm_prefetch_ = std::atoi(c) != 0;
   if (const char* c = std::getenv("TSG_POLL_YIELD")) e->poll_yield_ = std::atoi(c) != 0;
   if (const char* c = std::getenv("TSG_POP_SPIN_US")) e->pop_spin_us_ = std::max(0, std::min(std::atoi(c), 100000));
@@ -1954,15 +1971,9 @@ std::unique_ptr<Engine> Engine::create(std::shared_ptr<const Ruleset> rs, const 
     if (v >= kWireBlock) e->wire_strip_ = std::min<uint64_t>(static_cast<uint64_t>(v) / kWireBlock * kWireBlock, kWireMaxStrip);
   }
   if (e->host_profile_) g_scan_prof_on.store(true, std::memory_order_relaxed);
-  if (const char* c = std::getenv("TSG_K1_TAIL_ROUNDS")) {
-    const int v = std::atoi(c);
-    if (v >= 0 && v <= 16) e->k1_tail_rounds_ = static_cast<uint32_t>(v);
-  }
+  env_int("TSG_K1_TAIL_ROUNDS", 0, 16, &e->k1_tail_rounds_);
   if (const char* c = std::getenv("TSG_K1_TOP8")) e->k1_top8_ = std::max(0, std::min(2, std::atoi(c)));
-  if (const char* c = std::getenv("TSG_K2_HITS_PER_THREAD")) {
-    const int v = std::atoi(c);
-    if (v >= 1 && v <= 64) e->k2_hits_per_thread_ = static_cast<uint32_t>(v);
-  }
+  env_int("TSG_K2_HITS_PER_THREAD", 1, 64, &e->k2_hits_per_thread_);
   if (const char* c = std::getenv("TSG_K1_CHUNK")) {
     // K1's LDS hit record keeps (offset in the wave item) << kAnchorBits in
     // 32 bits and a wave item spans 64 lanes x 4 chunks: larger chunks are
@@ -2021,14 +2032,15 @@ Lane* Engine::acquire_lane(DeviceTables& dt, std::string* err) {
   std::unique_ptr<Lane> l(new Lane());
   l->device = dt.device;
   if (hipSetDevice(dt.device) != hipSuccess || hipStreamCreateWithFlags(&l->compute, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&l->copy, hipStreamNonBlocking) != hipSuccess || hipMalloc(&l->d_cnt, kCntBytes) != hipSuccess) {
+      hipStreamCreateWithFlags(&l->copy, hipStreamNonBlocking) != hipSuccess ||
+      !l->d_cnt.ensure(kCntBytes / sizeof(unsigned int), err)) {
     *err = "lane setup (streams, counters) failed";
     return nullptr;
   }
   for (auto& ev : l->ev) if (hipEventCreate(&ev) != hipSuccess) { *err = "hipEventCreate failed"; return nullptr; }
   if (k2_stats_) {
-    const size_t n = kK2Stat * std::max<size_t>(pf_.rules.size(), 1) * sizeof(unsigned long long);
-    if (hipMalloc(&l->d_k2s, n) != hipSuccess || hipMemset(l->d_k2s, 0, n) != hipSuccess) {
+    const size_t n = kK2Stat * std::max<size_t>(pf_.rules.size(), 1);
+    if (!l->d_k2s.ensure(n, err) || hipMemset(l->d_k2s.p, 0, n * sizeof(unsigned long long)) != hipSuccess) {
       *err = "K2 stats buffer";
       return nullptr;
     }
@@ -2082,394 +2094,467 @@ void Engine::release_call(CallCtx* cc) {
   free_calls_.push_back(cc);
 }
 
-// K1 + K2 + candidate D2H of one segment whose bytes are at d_data on the
-// lane's device (resident, or landed by the lane's upload), on the lane's
-// compute stream.  Returns when the segment's results are on the host.
-bool Engine::run_segment(DeviceTables& dt, Lane& ln, const Segment& sg, const void* d_data_v, const uint64_t* d_off_up,
-                         ScanStats* st, GpuOut* out, std::string* err, const std::function<void()>* while_gpu,
-                         K1Chain* chain, bool defer_copy, const StageIn* stage_in) {
-  const BatchInput& in = sg.in;
-  // this call's prologue copies (a small pinned batch, staged offsets): a
-  // local, so nothing staged for one call can outlive it on the pooled lane
-  // (a stage left on the lane by an early return was copied by the
-  // next caller's prologue from a freed pinned buffer)
-  StageIn stage = stage_in ? *stage_in : StageIn();
-  HIP_OK(hipSetDevice(dt.device));
-  const uint64_t total = in.offsets[in.nfiles];
-  const uint8_t* d_data = static_cast<const uint8_t*>(d_data_v);
-  if ((reinterpret_cast<uintptr_t>(d_data) & 15) != 0) { *err = "device data must be 16-byte aligned"; return false; }
+// What the phases of one run_segment call share.
+struct SegRun {
+  DeviceTables& dt;
+  Lane& ln;
+  const BatchInput& in;
+  ScanStats* st;
+  K1Chain* chain;
+  const uint8_t* d_data = nullptr;
+  uint64_t* d_off = nullptr;
+  // this call's prologue copies (a small pinned batch, staged offsets): here,
+  // not on the lane, so nothing staged for one call can outlive it on the
+  // pooled lane (a stage left on the lane by an early return was
+  // copied by the next caller's prologue from a freed pinned buffer)
+  StageIn stage;
+  std::chrono::steady_clock::time_point t0;   // TSG_HOST_PROFILE: where a segment's GPU time goes
+  // geometry
+  uint64_t total = 0;
+  uint32_t chunk = 0;
+  bool top8 = false;
+  unsigned long long nchunks = 0;
+  uint32_t ngroups = 0, nfidx = 0;
+  size_t kw_n = 0;
+  // of the current K1 attempt: one hit region per (group, workgroup)
+  uint32_t blocks = 0, nregions = 0, region_cap = 0;
+  std::unique_lock<std::mutex> chain_lk;
+  // of the current K2 attempt
+  uint32_t nsub = 0, osub = 0, k2_grid = 0;
+  uint32_t* k2_trace = nullptr;
+  double t_sync = 0;                          // host wall time from t0 to the results
+  float k1_ms = 0, k2_ms = 0;
+};
+
+namespace {
+
+constexpr uint32_t kK1Threads = 1024;
+
+// per-wave LDS hit buffers as large as the group's table leaves room for
+// (512 entries for the builtin rules; large config-5 groups get fewer,
+// further hits go straight to the workgroup's global region)
+size_t k1_lds_for(const K1Group& g, uint32_t h) {
+  return (kK1Threads / 64) * h * 4 + kMaxWaves * 4 + 16 + ((g.table_words16 * 2 + 15) & ~15u) + 256 + g.meta_bytes;
+}
+uint32_t k1_wave_hits(const K1Group& g) {
+  uint32_t h = kWaveHits;
+  while (h > kK1WaveHitsMin && k1_lds_for(g, h) > kLdsBytes) h /= 2;
+  return h;
+}
+size_t k1_lds_of(const K1Group& g) { return k1_lds_for(g, k1_wave_hits(g)); }
+
+#ifdef TSG_K1_PROBE
+void append_trace(const char* env, const std::vector<uint32_t>& tr) {
+  const char* fn = std::getenv(env);
+  FILE* fp = fn ? std::fopen(fn, "ab") : nullptr;
+  if (!fp) return;
+  std::fwrite(tr.data(), sizeof(uint32_t), tr.size(), fp);
+  std::fclose(fp);
+}
+#endif
+
+}  // namespace
+
+// K1's chunk and schedule level for the segment's bytes.
+bool Engine::seg_geometry(SegRun& r, GpuOut* out, std::string* err) {
+  r.total = r.in.offsets[r.in.nfiles];
+  if ((reinterpret_cast<uintptr_t>(r.d_data) & 15) != 0) { *err = "device data must be 16-byte aligned"; return false; }
   // top8 for uploaded segments only: HBM-resident pieces, whose K1 runs beside
   // the previous piece's K2 (K1Chain), ran slower with it (config 2 resident
   // 5.55 vs 6.06-6.65 ms per step, K1 3.72 vs 3.80 ms, profiles/r8l_*)
-  const int top8_req = sg.in.d_data ? 0 : k1_top8_;
-  const uint32_t kChunk = chunk_ ? chunk_ : k1_chunk_for(total, static_cast<uint32_t>(std::max(dt.sms, 1)) * 1024u, top8_req,
-                                                         sg.in.d_data != nullptr);
-  if (kChunk > k1_max_chunk(kItemChunks) || kChunk % 128 != 0) { *err = "K1 chunk exceeds the hit record's offset range"; return false; }
+  const int top8_req = r.in.d_data ? 0 : k1_top8_;
+  r.chunk = chunk_ ? chunk_ : k1_chunk_for(r.total, static_cast<uint32_t>(std::max(r.dt.sms, 1)) * 1024u, top8_req,
+                                           r.in.d_data != nullptr);
+  if (r.chunk > k1_max_chunk(kItemChunks) || r.chunk % 128 != 0) { *err = "K1 chunk exceeds the hit record's offset range"; return false; }
   // the kU = 8 bulk level (TSG_K1_TOP8) for launches of >= 2 GiB (2: any
   // launch, for tests), while an 8-chunk wave item fits the hit record's
   // offset bits
-  const bool top8 = (top8_req == 2 || (top8_req == 1 && total >= (2ull << 30))) && kChunk <= k1_max_chunk(8);
-  if ((k1_abl_ & kAblNoLoad) && total < (1u << 20) + 64) { *err = "TSG_K1_ABL no-load build needs a batch of >= 1 MiB"; return false; }
-  st->chunk_bytes = kChunk;
-  out->chunk = kChunk;
-  hipStream_t s = ln.compute;
-  const auto t_seg0 = std::chrono::steady_clock::now();   // TSG_HOST_PROFILE: where a segment's GPU time goes
-  // offsets: landed with the upload (d_off_up), or copied here (resident data)
-  uint64_t* d_off = const_cast<uint64_t*>(d_off_up);
-  if (!d_off) {
-    // staged through the lane's pinned buffer and copied by the segment
-    // prologue (StageIn): a hipMemcpyAsync from the caller's pageable array
-    // is a synchronous staged copy that held a resident driver thread up to
-    // ~1 ms while the other driver's passes ran (r5r host timelines)
-    if (!ensure(&ln.d_off, &ln.d_off_cap, in.nfiles + 1, err)) return false;
-    const size_t nb = (in.nfiles + 1) * sizeof(uint64_t);
-    if (ln.h_off_pin_cap[0] < in.nfiles + 1) {
-      if (ln.h_off_pin[0]) hipHostFree(ln.h_off_pin[0]);
-      ln.h_off_pin[0] = nullptr;
-      ln.h_off_pin_cap[0] = 0;
-      HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&ln.h_off_pin[0]), nb, hipHostMallocDefault));
-      ln.h_off_pin_cap[0] = in.nfiles + 1;
-    }
-    std::memcpy(ln.h_off_pin[0], in.offsets, nb);
-    void* off_dev = nullptr;
-    HIP_OK(hipHostGetDevicePointer(&off_dev, ln.h_off_pin[0], 0));
-    if (!off_dev || nb > 0xffffffffull) { *err = "pinned offsets staging has no device view"; return false; }
-    stage.off_src = static_cast<const uint8_t*>(off_dev);
-    stage.off_dst = reinterpret_cast<uint8_t*>(ln.d_off);
-    stage.off_bytes = nb;
-    d_off = ln.d_off;
+  r.top8 = (top8_req == 2 || (top8_req == 1 && r.total >= (2ull << 30))) && r.chunk <= k1_max_chunk(8);
+  if ((k1_abl_ & kAblNoLoad) && r.total < (1u << 20) + 64) { *err = "TSG_K1_ABL no-load build needs a batch of >= 1 MiB"; return false; }
+  r.nchunks = (r.total + r.chunk - 1) / r.chunk;
+  r.st->chunk_bytes = r.chunk;
+  out->chunk = r.chunk;
+  r.t0 = std::chrono::steady_clock::now();
+  return true;
+}
+
+// Resident data: the offsets are staged through the lane's pinned buffer and
+// copied by the segment prologue (StageIn): a hipMemcpyAsync from the
+// caller's pageable array is a synchronous staged copy that held a resident
+// driver thread up to ~1 ms while the other driver's passes ran (r5r host
+// timelines).
+bool Engine::seg_stage_offsets(SegRun& r, std::string* err) {
+  Lane& ln = r.ln;
+  if (!ln.d_off.ensure(r.in.nfiles + 1, err) || !ln.h_off_pin[0].ensure_offsets(r.in.nfiles, err)) return false;
+  const size_t nb = (r.in.nfiles + 1) * sizeof(uint64_t);
+  std::memcpy(ln.h_off_pin[0].p, r.in.offsets, nb);
+  if (!ln.h_off_pin[0].d || nb > 0xffffffffull) { *err = "pinned offsets staging has no device view"; return false; }
+  r.stage.off_src = static_cast<const uint8_t*>(ln.h_off_pin[0].d);
+  r.stage.off_dst = reinterpret_cast<uint8_t*>(ln.d_off.p);
+  r.stage.off_bytes = nb;
+  r.d_off = ln.d_off.p;
+  return true;
+}
+
+// The lane's scratch, grown to the segment's size.
+bool Engine::seg_size_scratch(SegRun& r, std::string* err) {
+  Lane& ln = r.ln;
+  const BatchInput& in = r.in;
+  const int sms = std::max(r.dt.sms, 1);
+  r.kw_n = static_cast<size_t>(std::max<uint32_t>(in.nfiles, 1)) * r.dt.kw_words;
+  r.ngroups = static_cast<uint32_t>(r.dt.k1g.size());
+  if (r.ngroups > kMaxK1Groups) { *err = "too many scan-DFA groups"; return false; }
+  ln.hit_cap = std::max<size_t>(ln.hit_cap, r.total / 256);   // ~1 hit per 670 B on source text
+  ln.over_cap = std::max<size_t>(ln.over_cap, r.total / 2048);
+  // K1's file index: entries for blocks 0 .. (total - 1) >> 16, plus one
+  r.nfidx = r.total ? static_cast<uint32_t>(((r.total - 1) >> kFidxShift) + 2) : 0u;
+  return ln.d_kw.ensure(r.kw_n, err) && ln.d_nl.ensure(std::max<unsigned long long>(r.nchunks, 1), err) &&
+         ln.d_cf.ensure(std::max<unsigned long long>(r.nchunks, 1), err) && ln.d_hits.ensure(ln.hit_cap, err) &&
+         ln.d_over.ensure(ln.over_cap, err) &&
+         ln.d_bh.ensure(2ull * sms * std::max<uint32_t>(r.ngroups, 1), err) &&
+         ln.d_ff.ensure(std::max<uint32_t>(in.nfiles, 1), err) &&
+         // deferred-output slots: kOutSlots per thread (x2 grid slack)
+         ln.d_ob.ensure(static_cast<size_t>(sms) * 1024 * 2 * kOutSlots, err) &&
+         (!file_index_ || !r.nfidx || ln.d_fidx.ensure(r.nfidx, err));
+}
+
+// K1's grid for this attempt, and the prologue: keyword bits, file flags,
+// counters, per-region hit counts zeroed (and a staged batch / offsets copied
+// in on the first attempt) in one launch.
+bool Engine::seg_prologue(SegRun& r, int attempt, std::string* err) {
+  Lane& ln = r.ln;
+  const uint64_t want_blocks = (r.nchunks + kK1Threads - 1) / kK1Threads;
+  // one resident workgroup per CU (the LDS table takes most of the CU's
+  // 160 KiB): a grid of at most one workgroup per CU, waves take items
+  r.blocks = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(want_blocks, static_cast<uint32_t>(r.dt.sms))));
+  r.st->k1_blocks = r.blocks;
+  r.st->k1_threads = kK1Threads;
+  r.st->table_in_lds = 1;
+  r.nregions = r.blocks * std::max<uint32_t>(r.ngroups, 1);
+  r.region_cap = static_cast<uint32_t>(std::min<size_t>(ln.hit_cap / r.nregions, 0xffffffffu));
+  Prologue pl{};
+  uint32_t* ptrs[4] = {ln.d_kw.p, ln.d_ff.p, reinterpret_cast<uint32_t*>(ln.d_cnt.p), ln.d_bh.p};
+  const uint32_t ns[4] = {static_cast<uint32_t>(r.kw_n), std::max<uint32_t>(r.in.nfiles, 1),
+                          static_cast<uint32_t>(kCntBytes / 4), r.nregions};
+  uint32_t mx = 0;
+  for (int k = 0; k < 4; ++k) { pl.p[k] = ptrs[k]; pl.n[k] = ns[k]; mx = std::max(mx, ns[k]); }
+  uint32_t rows = 4;
+  const StageIn& stage = r.stage;
+  if ((stage.bytes || stage.off_bytes) && attempt == 0) {   // a small pinned batch / offsets: staged by this launch
+    pl.src[0] = stage.src; pl.dst[0] = stage.dst;
+    pl.bytes[0] = static_cast<uint32_t>(stage.bytes); pl.zpad[0] = stage.bytes ? 64 : 0;   // (no pad when only offsets are staged)
+    pl.src[1] = stage.off_src; pl.dst[1] = stage.off_dst;
+    pl.bytes[1] = static_cast<uint32_t>(stage.off_bytes); pl.zpad[1] = 0;
+    mx = std::max<uint32_t>(mx, static_cast<uint32_t>(std::max(stage.bytes, stage.off_bytes) / 16 + 64));
+    rows = 6;
   }
+  hipLaunchKernelGGL(tsg_prologue, dim3(std::min<uint32_t>(256, (mx + 255) / 256), rows), dim3(256), 0, ln.compute, pl);
+  HIP_OK(hipGetLastError());
+  return true;
+}
+
+// Every K1 build this segment launches may use its dynamic LDS (set once per
+// build and device: DeviceTables::lds_set).
+bool Engine::seg_k1_lds_limits(SegRun& r, std::string* err) {
+  DeviceTables& dt = r.dt;
+  for (const K1Group& g : dt.k1g) {
+    const void* kfn = k1_kernel(k1_abl_, g.compressed);
+    if (!kfn) { *err = "unsupported K1 build (TSG_K1_ABL; the measurement builds are in the probe library)"; return false; }
+    if (!g.in_lds || k1_lds_of(g) > kLdsBytes) { *err = "K1 LDS budget exceeded"; return false; }
+    const int want = static_cast<int>(k1_lds_of(g));
+    bool set = false;
+    {
+      std::lock_guard<std::mutex> lk(dt.mu);
+      for (const auto& e : dt.lds_set) set = set || (e.first == kfn && e.second >= want);
+    }
+    if (!set) {
+      HIP_OK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, want));
+      std::lock_guard<std::mutex> lk(dt.mu);
+      dt.lds_set.emplace_back(kfn, want);
+    }
+  }
+  return true;
+}
+
+// The file index and one K1 launch per scan-DFA group, between ev[0] and
+// ev[1]; a K1Chain driver takes the chain's lock on its first attempt and
+// holds it until its K2 is queued (seg_launch_k2).
+bool Engine::seg_launch_k1(SegRun& r, int attempt, std::string* err) {
+  Lane& ln = r.ln;
+  DeviceTables& dt = r.dt;
+  const BatchInput& in = r.in;
+  hipStream_t s = ln.compute;
+  if (!seg_k1_lds_limits(r, err)) return false;
+  if (r.chain && attempt == 0) {
+    r.chain_lk = std::unique_lock<std::mutex>(r.chain->mu);
+    if (r.chain->last && chain_k1_ != 2) HIP_OK(hipStreamWaitEvent(s, r.chain->last, 0));   // (2: no wait, K1s overlap)
+  }
+  HIP_OK(hipEventRecord(ln.ev[0], s));
+  const uint32_t* a_fidx = nullptr;
+  if (file_index_ && r.nfidx && r.nchunks > 0) {          // (inside K1's timed window)
+    hipLaunchKernelGGL(tsg_file_index, dim3((r.nfidx + 255) / 256), dim3(256), 0, s, static_cast<const uint64_t*>(r.d_off),
+                       in.nfiles, ln.d_fidx.p, r.nfidx);
+    HIP_OK(hipGetLastError());
+    a_fidx = ln.d_fidx.p;
+  }
+  uint32_t launches = 0;
+  for (uint32_t gi = 0; gi < r.ngroups && r.nchunks > 0; ++gi) {
+    const K1Group& g = dt.k1g[gi];
+    const size_t lds = k1_lds_of(g);
+    uint32_t* a_items = ln.d_cnt.p + kItemCtrBase + 256 * gi;   // v3's work-item counters (zeroed with d_cnt)
+    unsigned long long a_total = r.total;
+    uint32_t a_nfiles = in.nfiles, a_ncls = g.nclasses, a_tw = g.table_words16;
+    uint32_t a_first = g.first_out, a_nmeta = k1_wave_hits(g), a_nlist = g.nlist, a_nkw = pf_.nkw;
+    uint32_t a_warm = (k1_abl_ & kAblLine64) ? g.warm_lines64 : g.warm_lines;
+    unsigned long long a_nchunks = r.nchunks;
+    uint32_t a_chunk = r.chunk;
+    uint32_t a_kww = dt.kw_words, a_kwbase = g.kw_base, a_primary = gi == 0;
+    const uint8_t* a_data = r.d_data;
+    unsigned long long* a_hits = ln.d_hits.p + static_cast<size_t>(gi) * r.blocks * r.region_cap;
+    uint32_t* a_bh = ln.d_bh.p + static_cast<size_t>(gi) * r.blocks;
+    uint16_t* a_next = g.next.p;
+    uint8_t* a_cls = g.cls.p;
+    OutMeta* a_meta = g.meta.p;
+    uint32_t* a_list = g.list.p;
+    uint32_t* a_ocnt = ln.d_cnt.p + 2;
+    uint32_t a_ocap = static_cast<uint32_t>(std::min<size_t>(ln.over_cap, 0xffffffffu));
+    uint32_t a_rcap = r.region_cap;
+    uint32_t a_tail = k1_tail_rounds_ | (r.top8 ? 0x100u : 0u);
+    // (the order and types of tsg_k1_scan_v3's parameters)
+    void* args[] = {&a_data, &a_total, &r.d_off, &a_nfiles, &a_next, &a_cls, &a_ncls, &a_tw, &a_first,
+                    &a_meta, &a_nmeta, &a_list, &a_nlist, &a_nkw, &a_warm, &a_chunk, &a_nchunks,
+                    &ln.d_kw.p, &a_kww, &a_kwbase, &a_primary, &a_hits, &a_bh, &a_rcap,
+                    &ln.d_over.p, &a_ocnt, &a_ocap, &ln.d_nl.p, &ln.d_cf.p, &ln.d_ff.p, &a_items, &ln.d_ob.p, &a_tail,
+                    &a_fidx};
+    HIP_OK(hipLaunchKernel(k1_kernel(k1_abl_, g.compressed), dim3(r.blocks), dim3(kK1Threads), args, lds, s));
+    ++launches;
+  }
+  HIP_OK(hipEventRecord(ln.ev[1], s));
+  r.st->k1_launches += launches;
+  return true;
+}
+
+// K2 follows K1 on the stream without a host round trip: its grid is sized
+// from the lane's previous segment (or the segment's bytes), and it reads the
+// per-region hit counts and the overflow count on the device.
+bool Engine::seg_launch_k2(SegRun& r, int a2, std::string* err) {
+  Lane& ln = r.ln;
+  DeviceTables& dt = r.dt;
+  hipStream_t s = ln.compute;
+  if (!ln.d_cands.ensure(ln.cand_cap, err)) return false;
+  if (a2 > 0) HIP_OK(hipMemsetAsync(ln.d_cnt.p + 1, 0, 4, s));   // (zeroed with the counters before K1)
+  // (K2's start is K1's end marker on the first attempt: a marker between
+  // two kernels costs ~5 us of device time on a small segment)
+  if (a2 > 0) HIP_OK(hipEventRecord(ln.ev[2], s));
+  const uint64_t per_block = 256ull * k2_hits_per_thread_;
+  const uint64_t maxr_est = ln.k2_maxr_per_byte > 0 ? static_cast<uint64_t>(ln.k2_maxr_per_byte * r.total) + 1
+                                                    : 2 * (r.total / 2048) / r.nregions + 1;
+  r.nsub = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(256, (maxr_est + per_block - 1) / per_block)));
+  r.osub = static_cast<uint32_t>(std::max<uint64_t>(16, std::min<uint64_t>(4096, (ln.k2_over_est + 1023) / 1024)));
+  // the region grid, then the overflow pool's workgroups, in one launch
+  r.k2_grid = r.nregions * r.nsub + r.osub;
+  const int k2v = (ln.d_k2s.p ? kK2Stats : 0) | k2_abl_;
+  r.k2_trace = ln.d_ob.p;                          // (probe builds: K1's deferred-output slots are free now)
+  const void* k2fn = k2v == 0 ? reinterpret_cast<const void*>(&tsg_k2_verify<0>)
+                   : k2v == kK2Stats ? reinterpret_cast<const void*>(&tsg_k2_verify<kK2Stats>)
+#ifdef TSG_K1_PROBE
+                   : k2v == kK2Trace ? reinterpret_cast<const void*>(&tsg_k2_verify<kK2Trace>)
+                   : k2v == kK2NoWalk ? reinterpret_cast<const void*>(&tsg_k2_verify<kK2NoWalk>)
+                   : k2v == (kK2Trace | kK2NoWalk) ? reinterpret_cast<const void*>(&tsg_k2_verify<kK2Trace | kK2NoWalk>)
+#endif
+                   : nullptr;
+  if (!k2fn) { *err = "unsupported K2 build (TSG_K2_ABL: probe library only)"; return false; }
+  if ((k2_abl_ & kK2Trace) && static_cast<size_t>(r.k2_grid) * 4 * 8 > ln.d_ob.cap / 2) { *err = "K2 trace buffer too small"; return false; }
+  uint32_t a_nf = r.in.nfiles, a_chunk = r.chunk, a_rcap = r.region_cap, a_nreg = r.nregions, a_nsub = r.nsub;
+  uint32_t a_ocap = static_cast<uint32_t>(std::min<size_t>(ln.over_cap, 0xffffffffu)), a_kww = dt.kw_words;
+  uint32_t a_ccap = static_cast<uint32_t>(ln.cand_cap);
+  const uint8_t* a_data = r.d_data;
+  unsigned int* a_over_cnt = ln.d_cnt.p + 2;
+  unsigned long long a_total = r.total;
+  // (the order and types of tsg_k2_verify's parameters)
+  void* k2args[] = {&a_data, &a_total, &r.d_off, &a_nf, &ln.d_cf.p, &a_chunk,
+                    &ln.d_hits.p, &ln.d_bh.p, &a_rcap, &a_nreg,
+                    &a_nsub, &ln.d_over.p, &a_over_cnt, &a_ocap,
+                    &dt.anchors.p, &dt.rule_kw.p, &ln.d_kw.p, &a_kww, &dt.v_next.p, &dt.v_cls.p,
+                    &ln.d_cands.p, &ln.d_cnt.p, &a_ccap, &ln.d_k2s.p, &r.k2_trace};
+  HIP_OK(hipLaunchKernel(k2fn, dim3(r.k2_grid), dim3(256), k2args, 0, s));
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipEventRecord(ln.ev[3], s));
+  if (r.chain_lk.owns_lock()) {            // the other driver's next K1 follows this K2
+    r.chain->last = chain_k1_ == 0 ? ln.ev[3] : ln.ev[1];
+    r.chain_lk.unlock();
+  }
+  return true;
+}
+
+// Everything to the host in one round trip: per-region hit counts, the
+// counters (candidates, overflow hits, LDS check), file flags, newline counts
+// and the candidates (as many as fit); returns when they have arrived, with
+// the passes' times.
+bool Engine::seg_readback_wait(SegRun& r, int a2, std::string* err) {
+  Lane& ln = r.ln;
+  hipStream_t s = ln.compute;
+  const uint32_t nfiles = r.in.nfiles;
+  if (!ln.rb_bh.ensure_readback(r.nregions * sizeof(uint32_t), err) || !ln.rb_c2.ensure_readback(16, err) ||
+      !ln.rb_ff.ensure_readback(nfiles * sizeof(uint32_t), err) ||
+      !ln.rb_nl.ensure_readback(r.nchunks * sizeof(uint16_t), err) ||
+      !ln.rb_cands.ensure_readback(ln.cand_cap * sizeof(CandDev), err)) return false;
+  Readbacks rb;
+  rb.add(ln.d_bh.p, ln.rb_bh, r.nregions);
+  rb.add(ln.d_cnt.p, ln.rb_c2, 4);
+  rb.add(ln.d_ff.p, ln.rb_ff, nfiles);
+  rb.add(ln.d_nl.p, ln.rb_nl, (r.nchunks + 1) / 2);
+  rb.add(ln.d_cands.p, ln.rb_cands, ln.cand_cap * (sizeof(CandDev) / 4), ln.d_cnt.p + 1, sizeof(CandDev) / 4);
+  if (!rb.launch(s, err)) return false;
+  if (r.chain) {
+    // polled with short sleeps: a blocking-sync event woke its driver
+    // 0.3-1.2 ms after the passes ended (profiles/rd5e_bench_c2prof.log)
+    if (!ln.ev_sync) HIP_OK(hipEventCreateWithFlags(&ln.ev_sync, hipEventDisableTiming));
+    HIP_OK(hipEventRecord(ln.ev_sync, s));
+    for (;;) {
+      const hipError_t q = hipEventQuery(ln.ev_sync);
+      if (q == hipSuccess) break;
+      if (q != hipErrorNotReady) HIP_OK(q);
+      // yielding only while the confirm pool is idle: on a box whose
+      // CPU share is a cgroup quota, drivers spinning beside a busy pool
+      // spend the pool's quota (config 5 resident steps 16.9-20.2 ms)
+      if (poll_yield_ && (!ln.pool_idle || ln.pool_idle->load(std::memory_order_relaxed))) std::this_thread::yield();
+      else std::this_thread::sleep_for(std::chrono::microseconds(10));
+    }
+  } else {
+    // (round 5 measured a host-mapped completion word written by the
+    // readback's last block, spun on instead: the events' times were then
+    // not yet ready and waiting for them cost a one-file batch 0.25 ms,
+    // profiles/r5i_small.log; the stream synchronization stays)
+    HIP_OK(hipStreamSynchronize(s));
+  }
+  r.t_sync = ms_since(r.t0);
+  if (ln.rb_c2.as<const uint32_t>()[3] != 0) { *err = "K1: dynamic LDS does not start at address 0"; return false; }
+  HIP_OK(hipEventElapsedTime(&r.k1_ms, ln.ev[0], ln.ev[1]));
+  HIP_OK(hipEventElapsedTime(&r.k2_ms, a2 > 0 ? ln.ev[2] : ln.ev[1], ln.ev[3]));
+  if (a2 == 0) r.st->k1_ms += r.k1_ms;
+  r.st->k2_ms += r.k2_ms;
+  return true;
+}
+
+// The segment's results to `out` (still in the lane's readback buffers with
+// defer_copy), K2's grid estimate for the lane's next segment, the stats.
+void Engine::seg_hand_off(SegRun& r, uint32_t ncands, uint32_t nover, bool defer_copy, GpuOut* out) {
+  Lane& ln = r.ln;
+  const uint32_t* h_bh = ln.rb_bh.as<const uint32_t>();
+  uint64_t nhits = 0;
+  uint32_t maxr = 0;
+  for (uint32_t k = 0; k < r.nregions; ++k) { nhits += h_bh[k]; maxr = std::max(maxr, std::min(h_bh[k], r.region_cap)); }
+  ln.k2_maxr_per_byte = r.total ? static_cast<double>(maxr) * 1.25 / static_cast<double>(r.total) : 0.0;
+  ln.k2_over_est = nover;
+  r.st->hits += nhits;
+  auto t_d2h = std::chrono::steady_clock::now();
+  out->rb_cands = ln.rb_cands.as<CandDev>();
+  out->rb_ff = ln.rb_ff.as<uint32_t>();
+  out->rb_nl = ln.rb_nl.as<uint16_t>();
+  out->n_cands = ncands;
+  out->n_ff = r.in.nfiles;
+  out->n_nl = r.nchunks;
+  out->deferred = true;
+  if (!defer_copy) out->finish_copy();
+  r.st->d2h_ms += ms_since(t_d2h);
+  if (host_profile_)
+    std::fprintf(stderr, "[tsg seg] %.1f MB %u files: wall to results %.3f ms (K1 %.3f, K2 %.3f, K2 grid %u+%u), "
+                 "copy-out %.3f ms, total %.3f ms\n", r.total / 1e6, r.in.nfiles, r.t_sync, r.k1_ms, r.k2_ms,
+                 r.nregions * r.nsub, r.osub, ms_since(t_d2h), ms_since(r.t0));
+  r.st->candidates += ncands;
+}
+
+#ifdef TSG_K1_PROBE
+// Probe builds: the passes' per-wave stamps appended to the trace files.
+bool Engine::seg_write_traces(SegRun& r, std::string* err) {
+  Lane& ln = r.ln;
+  if (k2_abl_ & kK2Trace) {
+    // K2's stamps to $TSG_K2_TRACE_FILE as [waves, 0, 0, 0][8 x waves] uint32
+    const size_t waves = static_cast<size_t>(r.k2_grid) * 4;
+    std::vector<uint32_t> tr(4 + 8 * waves, 0);
+    tr[0] = static_cast<uint32_t>(waves);
+    HIP_OK(hipMemcpy(tr.data() + 4, r.k2_trace, 8 * waves * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    append_trace("TSG_K2_TRACE_FILE", tr);
+  }
+  if (k1_abl_ & kAblTrace) {
+    // the K1 launch's stamps (kAblTrace) to $TSG_K1_TRACE_FILE as
+    // [blocks, items, nchunks, chunk][4 x blocks][kTraceItemWords x items] uint32
+    const uint32_t items = static_cast<uint32_t>(std::min<uint64_t>(kTraceItemCap, 3 * (r.nchunks + 63) / 64 + 64));
+    std::vector<uint32_t> tr(4 + 4 * static_cast<size_t>(r.blocks) + kTraceItemWords * static_cast<size_t>(items), 0);
+    tr[0] = r.blocks; tr[1] = items; tr[2] = static_cast<uint32_t>(r.nchunks); tr[3] = r.chunk;
+    uint32_t* d_tr = ln.d_ob.p + static_cast<size_t>(r.blocks) * kK1Threads * kOutSlots;
+    HIP_OK(hipMemcpy(tr.data() + 4, d_tr, (tr.size() - 4) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    append_trace("TSG_K1_TRACE_FILE", tr);
+    HIP_OK(hipMemset(d_tr, 0, (tr.size() - 4) * sizeof(uint32_t)));
+  }
+  return true;
+}
+#endif
+
+// TSG_K2_STATS: the lane's per-rule K2 counters folded into the engine's, and zeroed.
+bool Engine::fold_k2_stats(Lane& ln, std::string* err) {
+  std::vector<unsigned long long> h(kK2Stat * pf_.rules.size());
+  HIP_OK(hipMemcpy(h.data(), ln.d_k2s.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemset(ln.d_k2s.p, 0, h.size() * sizeof(unsigned long long)));
+  std::lock_guard<std::mutex> lk(k2s_mu_);
+  if (k2s_.size() < h.size()) k2s_.resize(h.size(), 0);
+  for (size_t i = 0; i < h.size(); ++i)
+    k2s_[i] = i % kK2Stat == 4 ? std::max(k2s_[i], h[i]) : k2s_[i] + h[i];
+  return true;
+}
+
+// K1 + K2 + candidate D2H of one segment whose bytes are at d_data on the
+// lane's device (resident, or landed by the lane's upload), on the lane's
+// compute stream.  Returns when the segment's results are on the host.  One
+// readback + sync per segment: an overflowed hit pool or candidate buffer is
+// seen afterwards, grown, and the pass run again.
+bool Engine::run_segment(DeviceTables& dt, Lane& ln, const Segment& sg, const void* d_data, const uint64_t* d_off_up,
+                         ScanStats* st, GpuOut* out, std::string* err, const std::function<void()>* while_gpu,
+                         K1Chain* chain, bool defer_copy, const StageIn* stage_in) {
+  SegRun r{dt, ln, sg.in, st, chain};
+  r.d_data = static_cast<const uint8_t*>(d_data);
+  r.d_off = const_cast<uint64_t*>(d_off_up);
+  if (stage_in) r.stage = *stage_in;
+  HIP_OK(hipSetDevice(dt.device));
+  if (!seg_geometry(r, out, err)) return false;
+  // offsets: landed with the upload (d_off_up), or staged here (resident data)
+  if (!r.d_off && !seg_stage_offsets(r, err)) return false;
   // test hook (tsg_test_inject_segment_failures): fail here, after the
   // offsets were staged and before any launch, as a failed allocation would
   for (uint32_t k = inject_fail_.load(); k > 0;) {
     if (inject_fail_.compare_exchange_weak(k, k - 1)) { *err = "injected segment failure (test hook)"; return false; }
   }
-  const size_t kw_n = static_cast<size_t>(std::max<uint32_t>(in.nfiles, 1)) * dt.kw_words;
-  if (!ensure(&ln.d_kw, &ln.d_kw_cap, kw_n, err)) return false;
-  const unsigned long long nchunks = (total + kChunk - 1) / kChunk;
-  if (!ensure(&ln.d_nl, &ln.d_nl_cap, std::max<unsigned long long>(nchunks, 1), err)) return false;
-  if (!ensure(&ln.d_cf, &ln.d_cf_cap, std::max<unsigned long long>(nchunks, 1), err)) return false;
-  ln.hit_cap = std::max<size_t>(ln.hit_cap, total / 256);   // ~1 hit per 670 B on source text
-  if (!ensure(&ln.d_hits, &ln.d_hits_cap, ln.hit_cap, err)) return false;
-  ln.over_cap = std::max<size_t>(ln.over_cap, total / 2048);
-  if (!ensure(&ln.d_over, &ln.d_over_cap, ln.over_cap, err)) return false;
-  const uint32_t ngroups = static_cast<uint32_t>(dt.k1g.size());
-  if (ngroups > kMaxK1Groups) { *err = "too many scan-DFA groups"; return false; }
-  if (!ensure(&ln.d_bh, &ln.d_bh_cap, 2ull * std::max(dt.sms, 1) * std::max<uint32_t>(ngroups, 1), err)) return false;
-  if (!ensure(&ln.d_ff, &ln.d_ff_cap, std::max<uint32_t>(in.nfiles, 1), err)) return false;
-  // deferred-output slots: kOutSlots per thread (x2 grid slack)
-  if (!ensure(&ln.d_ob, &ln.d_ob_cap, static_cast<size_t>(std::max(dt.sms, 1)) * 1024 * 2 * kOutSlots, err))
-    return false;
-  // K1's file index: entries for blocks 0 .. (total - 1) >> 16, plus one
-  const uint32_t nfidx = total ? static_cast<uint32_t>(((total - 1) >> kFidxShift) + 2) : 0u;
-  if (file_index_ && nfidx && !ensure(&ln.d_fidx, &ln.d_fidx_cap, nfidx, err)) return false;
-
-  const uint32_t sms = static_cast<uint32_t>(dt.sms);
-  const Prefilter& pf = pf_;
+  if (!seg_size_scratch(r, err)) return false;
   for (int attempt = 0; attempt < 3; ++attempt) {
-    constexpr uint32_t nthr = 1024;
-    const uint64_t want_blocks = (nchunks + nthr - 1) / nthr;
-    // one resident workgroup per CU (the LDS table takes most of the CU's
-    // 160 KiB): a grid of exactly one workgroup per CU, waves take items
-    // K1Chain (resident pieces): k1_reserve_cus_ CUs left out of the grid, so
-    // the previous piece's K2 and readback kernels, queued behind its K1 and
-    // ready while this K1 runs, find a CU at once -- K1's 1024 threads x 122
-    // VGPRs fill a CU's register file, and those kernels otherwise waited for
-    // the whole launch (0.8 ms per piece, profiles/r8o_*, r9d_*)
-    const uint32_t reserve = chain && sms > 2 * k1_reserve_cus_ ? k1_reserve_cus_ : 0u;
-    const uint32_t blocks = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(want_blocks, sms - reserve)));
-    st->k1_blocks = blocks;
-    st->k1_threads = nthr;
-    st->table_in_lds = 1;
-    // one hit region per (group, workgroup); K2 walks all of them
-    const uint32_t nregions = blocks * std::max<uint32_t>(ngroups, 1);
-    const uint32_t region_cap = static_cast<uint32_t>(std::min<size_t>(ln.hit_cap / nregions, 0xffffffffu));
-    {
-      // keyword bits, file flags, counters, per-region hit counts: one launch
-      Prologue pl{};
-      uint32_t* ptrs[4] = {ln.d_kw, ln.d_ff, reinterpret_cast<uint32_t*>(ln.d_cnt), ln.d_bh};
-      const uint32_t ns[4] = {static_cast<uint32_t>(kw_n), std::max<uint32_t>(in.nfiles, 1),
-                              static_cast<uint32_t>(kCntBytes / 4), nregions};
-      uint32_t mx = 0;
-      for (int k = 0; k < 4; ++k) { pl.p[k] = ptrs[k]; pl.n[k] = ns[k]; mx = std::max(mx, ns[k]); }
-      uint32_t rows = 4;
-      if ((stage.bytes || stage.off_bytes) && attempt == 0) {   // a small pinned batch / offsets: staged by this launch
-        pl.src[0] = stage.src; pl.dst[0] = stage.dst;
-        pl.bytes[0] = static_cast<uint32_t>(stage.bytes); pl.zpad[0] = stage.bytes ? 64 : 0;   // (no pad when only offsets are staged)
-        pl.src[1] = stage.off_src; pl.dst[1] = stage.off_dst;
-        pl.bytes[1] = static_cast<uint32_t>(stage.off_bytes); pl.zpad[1] = 0;
-        mx = std::max<uint32_t>(mx, static_cast<uint32_t>(std::max(stage.bytes, stage.off_bytes) / 16 + 64));
-        rows = 6;
-      }
-      hipLaunchKernelGGL(tsg_prologue, dim3(std::min<uint32_t>(256, (mx + 255) / 256), rows), dim3(256), 0, s, pl);
-      HIP_OK(hipGetLastError());
-    }
-    // per-wave LDS hit buffers as large as the group's table leaves room for
-    // (512 entries for the builtin rules; large config-5 groups get fewer,
-    // further hits go straight to the workgroup's global region)
-    auto lds_for = [&](const K1Group& g, uint32_t h) -> size_t {
-      return (nthr / 64) * h * 4 + kMaxWaves * 4 + 16 + ((g.table_words16 * 2 + 15) & ~15u) + 256 + g.meta_bytes;
-    };
-    auto hits_of = [&](const K1Group& g) -> uint32_t {
-      uint32_t h = kWaveHits;
-      while (h > kK1WaveHitsMin && lds_for(g, h) > kLdsBytes) h /= 2;
-      return h;
-    };
-    auto lds_of = [&](const K1Group& g) -> size_t { return lds_for(g, hits_of(g)); };
-    for (uint32_t gi = 0; gi < ngroups; ++gi) {
-      const K1Group& g = dt.k1g[gi];
-      const void* kfn = k1_kernel(k1_abl_, g.compressed);
-      if (!kfn) { *err = "unsupported K1 build (TSG_K1_ABL; the measurement builds are in the probe library)"; return false; }
-      if (!g.in_lds || lds_of(g) > kLdsBytes) { *err = "K1 LDS budget exceeded"; return false; }
-      const int want = static_cast<int>(lds_of(g));
-      bool set = false;
-      {
-        std::lock_guard<std::mutex> lk(dt.mu);
-        for (const auto& e : dt.lds_set) set = set || (e.first == kfn && e.second >= want);
-      }
-      if (!set) {
-        HIP_OK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        std::lock_guard<std::mutex> lk(dt.mu);
-        dt.lds_set.emplace_back(kfn, want);
-      }
-    }
-    std::unique_lock<std::mutex> chain_lk;
-    if (chain && attempt == 0) {
-      chain_lk = std::unique_lock<std::mutex>(chain->mu);
-      if (chain->last && chain_k1_ != 2) HIP_OK(hipStreamWaitEvent(s, chain->last, 0));   // (2: no wait, K1s overlap)
-    }
-    HIP_OK(hipEventRecord(ln.ev[0], s));
-    const uint32_t* a_fidx = nullptr;
-    if (file_index_ && nfidx && nchunks > 0) {          // (inside K1's timed window)
-      hipLaunchKernelGGL(tsg_file_index, dim3((nfidx + 255) / 256), dim3(256), 0, s, static_cast<const uint64_t*>(d_off),
-                         in.nfiles, ln.d_fidx, nfidx);
-      HIP_OK(hipGetLastError());
-      a_fidx = ln.d_fidx;
-    }
-    uint32_t launches = 0;
-    for (uint32_t gi = 0; gi < ngroups && nchunks > 0; ++gi) {
-      const K1Group& g = dt.k1g[gi];
-      const size_t lds = lds_of(g);
-      uint32_t* a_items = ln.d_cnt + kItemCtrBase + 256 * gi;   // v3's work-item counters (zeroed with d_cnt)
-      unsigned long long a_total = total;
-      uint32_t a_nfiles = in.nfiles, a_ncls = g.nclasses, a_tw = g.table_words16;
-      uint32_t a_first = g.first_out, a_nmeta = hits_of(g), a_nlist = g.nlist, a_nkw = pf.nkw;
-      uint32_t a_warm = (k1_abl_ & kAblLine64) ? g.warm_lines64 : g.warm_lines;
-      unsigned long long a_nchunks = nchunks;
-      uint32_t a_chunk = kChunk;
-      uint32_t a_kww = dt.kw_words, a_kwbase = g.kw_base, a_primary = gi == 0;
-      const uint8_t* a_data = d_data;
-      unsigned long long* a_hits = ln.d_hits + static_cast<size_t>(gi) * blocks * region_cap;
-      uint32_t* a_bh = ln.d_bh + static_cast<size_t>(gi) * blocks;
-      uint16_t* a_next = g.next;
-      uint8_t* a_cls = g.cls;
-      OutMeta* a_meta = g.meta;
-      uint32_t* a_list = g.list;
-      uint32_t* a_ocnt = ln.d_cnt + 2;
-      uint32_t a_ocap = static_cast<uint32_t>(std::min<size_t>(ln.over_cap, 0xffffffffu));
-      uint32_t a_rcap = region_cap;
-      uint32_t a_tail = k1_tail_rounds_ | (top8 ? 0x100u : 0u);
-      void* args[] = {&a_data, &a_total, &d_off, &a_nfiles, &a_next, &a_cls, &a_ncls, &a_tw, &a_first,
-                      &a_meta, &a_nmeta, &a_list, &a_nlist, &a_nkw, &a_warm, &a_chunk, &a_nchunks,
-                      &ln.d_kw, &a_kww, &a_kwbase, &a_primary, &a_hits, &a_bh, &a_rcap,
-                      &ln.d_over, &a_ocnt, &a_ocap, &ln.d_nl, &ln.d_cf, &ln.d_ff, &a_items, &ln.d_ob, &a_tail,
-                      &a_fidx};
-      HIP_OK(hipLaunchKernel(k1_kernel(k1_abl_, g.compressed), dim3(blocks), dim3(nthr), args, lds, s));
-      ++launches;
-    }
-    HIP_OK(hipEventRecord(ln.ev[1], s));
-    st->k1_launches += launches;
-    // K2 follows K1 on the stream without a host round trip: its grid is
-    // sized from the lane's previous segment (or the segment's bytes), and
-    // it reads the per-region hit counts and the overflow count on the
-    // device; one readback + sync per segment.  An overflowed hit pool or
-    // candidate buffer is seen afterwards and re-run (grown).
+    if (!seg_prologue(r, attempt, err) || !seg_launch_k1(r, attempt, err)) return false;
     bool rerun_k1 = false;
     for (int a2 = 0; a2 < 3 && !rerun_k1; ++a2) {
-      if (!ensure(&ln.d_cands, &ln.d_cands_cap, ln.cand_cap, err)) return false;
-      if (a2 > 0) HIP_OK(hipMemsetAsync(ln.d_cnt + 1, 0, 4, s));   // (zeroed with the counters before K1)
-      // (K2's start is K1's end marker on the first attempt: a marker between
-      // two kernels costs ~5 us of device time on a small segment)
-      if (a2 > 0) HIP_OK(hipEventRecord(ln.ev[2], s));
-      const uint64_t per_block = 256ull * k2_hits_per_thread_;
-      const uint64_t maxr_est = ln.k2_maxr_per_byte > 0 ? static_cast<uint64_t>(ln.k2_maxr_per_byte * total) + 1
-                                                        : 2 * (total / 2048) / nregions + 1;
-      const uint32_t nsub = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(256, (maxr_est + per_block - 1) / per_block)));
-      const uint32_t osub = static_cast<uint32_t>(std::max<uint64_t>(16, std::min<uint64_t>(4096, (ln.k2_over_est + 1023) / 1024)));
-      const uint32_t ccap = static_cast<uint32_t>(ln.cand_cap);
-      const uint32_t ocap = static_cast<uint32_t>(std::min<size_t>(ln.over_cap, 0xffffffffu));
-      // the region grid, then the overflow pool's workgroups, in one launch
-      const uint32_t k2_grid = nregions * nsub + osub;
-      const int k2v = (ln.d_k2s ? kK2Stats : 0) | k2_abl_;
-      uint32_t* k2_trace = ln.d_ob;                    // (probe builds: K1's deferred-output slots are free now)
-      const void* k2fn = k2v == 0 ? reinterpret_cast<const void*>(&tsg_k2_verify<0>)
-                       : k2v == kK2Stats ? reinterpret_cast<const void*>(&tsg_k2_verify<kK2Stats>)
-#ifdef TSG_K1_PROBE
-                       : k2v == kK2Trace ? reinterpret_cast<const void*>(&tsg_k2_verify<kK2Trace>)
-                       : k2v == kK2NoWalk ? reinterpret_cast<const void*>(&tsg_k2_verify<kK2NoWalk>)
-                       : k2v == (kK2Trace | kK2NoWalk) ? reinterpret_cast<const void*>(&tsg_k2_verify<kK2Trace | kK2NoWalk>)
-#endif
-                       : nullptr;
-      if (!k2fn) { *err = "unsupported K2 build (TSG_K2_ABL: probe library only)"; return false; }
-      if ((k2_abl_ & kK2Trace) && static_cast<size_t>(k2_grid) * 4 * 8 > ln.d_ob_cap / 2) { *err = "K2 trace buffer too small"; return false; }
-      {
-        const uint32_t a_nf = in.nfiles, a_chunk = kChunk, a_rcap = region_cap, a_nreg = nregions, a_nsub = nsub;
-        const uint32_t a_ocap = ocap, a_kww = dt.kw_words, a_ccap = ccap;
-        const uint8_t* a_data = d_data;
-        unsigned int* a_over_cnt = ln.d_cnt + 2;
-        unsigned long long a_total = total;
-        void* k2args[] = {&a_data, &a_total, &d_off, const_cast<uint32_t*>(&a_nf), &ln.d_cf, const_cast<uint32_t*>(&a_chunk),
-                          &ln.d_hits, &ln.d_bh, const_cast<uint32_t*>(&a_rcap), const_cast<uint32_t*>(&a_nreg),
-                          const_cast<uint32_t*>(&a_nsub), &ln.d_over, &a_over_cnt, const_cast<uint32_t*>(&a_ocap),
-                          &dt.anchors, &dt.rule_kw, &ln.d_kw, const_cast<uint32_t*>(&a_kww), &dt.v_next, &dt.v_cls,
-                          &ln.d_cands, &ln.d_cnt, const_cast<uint32_t*>(&a_ccap), &ln.d_k2s, &k2_trace};
-        HIP_OK(hipLaunchKernel(k2fn, dim3(k2_grid), dim3(256), k2args, 0, s));
-      }
-      HIP_OK(hipGetLastError());
-      HIP_OK(hipEventRecord(ln.ev[3], s));
-      if (chain_lk.owns_lock()) {            // the other driver's next K1 follows this K2
-        chain->last = chain_k1_ == 0 ? ln.ev[3] : ln.ev[1];
-        chain_lk.unlock();
-      }
+      if (!seg_launch_k2(r, a2, err)) return false;
       // (before this segment's readbacks are queued: the callback may copy
       // the lane's previous segment out of the readback buffers)
       if (while_gpu && *while_gpu) {
         (*while_gpu)();
         while_gpu = nullptr;
       }
-      // everything to the host in one round trip: per-region hit counts, the
-      // counters (candidates, overflow hits, LDS check), file flags, newline
-      // counts and the candidates (as many as fit)
-      if (!ensure_pinned(&ln.rb_bh, nregions * sizeof(uint32_t), err) || !ensure_pinned(&ln.rb_c2, 16, err) ||
-          !ensure_pinned(&ln.rb_ff, in.nfiles * sizeof(uint32_t), err) ||
-          !ensure_pinned(&ln.rb_nl, nchunks * sizeof(uint16_t), err) ||
-          !ensure_pinned(&ln.rb_cands, ln.cand_cap * sizeof(CandDev), err)) return false;
-      if (chain && readback_dma_) {
-        // K1Chain: the next piece's K1 (other driver) holds every CU's
-        // register file until its launch ends, so a readback kernel queued
-        // behind this K2 waited for it (0.7-0.85 ms per resident piece,
-        // profiles/r8o_*); copies on the DMA engines need no CU.  The
-        // candidates go whole (the buffer's capacity, not the count).
-        HIP_OK(hipMemcpyAsync(ln.rb_bh.p, ln.d_bh, nregions * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIP_OK(hipMemcpyAsync(ln.rb_c2.p, ln.d_cnt, 16, hipMemcpyDeviceToHost, s));
-        HIP_OK(hipMemcpyAsync(ln.rb_ff.p, ln.d_ff, in.nfiles * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIP_OK(hipMemcpyAsync(ln.rb_nl.p, ln.d_nl, ((nchunks + 1) / 2) * 4, hipMemcpyDeviceToHost, s));
-        HIP_OK(hipMemcpyAsync(ln.rb_cands.p, ln.d_cands, ln.cand_cap * sizeof(CandDev), hipMemcpyDeviceToHost, s));
-      } else {
-        Readbacks rb;
-        rb.add(ln.d_bh, ln.rb_bh, nregions);
-        rb.add(ln.d_cnt, ln.rb_c2, 4);
-        rb.add(ln.d_ff, ln.rb_ff, in.nfiles);
-        rb.add(ln.d_nl, ln.rb_nl, (nchunks + 1) / 2);
-        rb.add(ln.d_cands, ln.rb_cands, ln.cand_cap * (sizeof(CandDev) / 4), ln.d_cnt + 1, sizeof(CandDev) / 4);
-        if (!rb.launch(s, err)) return false;
-      }
-      if (chain) {
-        // polled with short sleeps: a blocking-sync event woke its driver
-        // 0.3-1.2 ms after the passes ended (profiles/rd5e_bench_c2prof.log)
-        if (!ln.ev_sync) HIP_OK(hipEventCreateWithFlags(&ln.ev_sync, hipEventDisableTiming));
-        HIP_OK(hipEventRecord(ln.ev_sync, s));
-        for (;;) {
-          const hipError_t q = hipEventQuery(ln.ev_sync);
-          if (q == hipSuccess) break;
-          if (q != hipErrorNotReady) HIP_OK(q);
-          // yielding only while the confirm pool is idle: on a box whose
-          // CPU share is a cgroup quota, drivers spinning beside a busy pool
-          // spend the pool's quota (config 5 resident steps 16.9-20.2 ms)
-          if (poll_yield_ && (!ln.pool_idle || ln.pool_idle->load(std::memory_order_relaxed))) std::this_thread::yield();
-          else std::this_thread::sleep_for(std::chrono::microseconds(10));
-        }
-      } else {
-        // (round 5 measured a host-mapped completion word written by the
-        // readback's last block, spun on instead: the events' times were then
-        // not yet ready and waiting for them cost a one-file batch 0.25 ms,
-        // profiles/r5i_small.log; the stream synchronization stays)
-        HIP_OK(hipStreamSynchronize(s));
-      }
-      const double t_k1_sync = ms_since(t_seg0);
-      const uint32_t* h_bh = ln.rb_bh.as<const uint32_t>();
+      if (!seg_readback_wait(r, a2, err)) return false;
       const uint32_t* h_cnt = ln.rb_c2.as<const uint32_t>();
-      if (h_cnt[3] != 0) { *err = "K1: dynamic LDS does not start at address 0"; return false; }
-      float k1 = 0, k2 = 0;
-      HIP_OK(hipEventElapsedTime(&k1, ln.ev[0], ln.ev[1]));
-      HIP_OK(hipEventElapsedTime(&k2, a2 > 0 ? ln.ev[2] : ln.ev[1], ln.ev[3]));
-      if (a2 == 0) st->k1_ms += k1;
-      st->k2_ms += k2;
-      const uint32_t nover = h_cnt[2];
+      const uint32_t nover = h_cnt[2], ncands = h_cnt[1];
       if (nover > ln.over_cap) {
         // the overflow pool (shared by every workgroup) was too small: grow it
         // to the exact need and run K1 again.  Growth follows the batch's
         // total hit count, not the fullest region times the region count.
         ln.over_cap = static_cast<size_t>(nover) * 5 / 4 + 1024;
-        if (!ensure(&ln.d_over, &ln.d_over_cap, ln.over_cap, err)) return false;
+        if (!ln.d_over.ensure(ln.over_cap, err)) return false;
         rerun_k1 = true;
         break;
       }
-      const unsigned int c2 = h_cnt[1];
-      if (c2 > ln.cand_cap) { ln.cand_cap = static_cast<size_t>(c2) * 5 / 4 + 1024; continue; }
-      uint64_t nhits = 0;
-      uint32_t maxr = 0;
-      for (uint32_t r = 0; r < nregions; ++r) { nhits += h_bh[r]; maxr = std::max(maxr, std::min(h_bh[r], region_cap)); }
-      ln.k2_maxr_per_byte = total ? static_cast<double>(maxr) * 1.25 / static_cast<double>(total) : 0.0;
-      ln.k2_over_est = nover;
-      st->hits += nhits;
-      auto t_d2h = std::chrono::steady_clock::now();
-      out->rb_cands = ln.rb_cands.as<CandDev>();
-      out->rb_ff = ln.rb_ff.as<uint32_t>();
-      out->rb_nl = ln.rb_nl.as<uint16_t>();
-      out->n_cands = c2;
-      out->n_ff = in.nfiles;
-      out->n_nl = nchunks;
-      out->deferred = true;
-      if (!defer_copy) out->finish_copy();
-      st->d2h_ms += ms_since(t_d2h);
-      if (host_profile_)
-        std::fprintf(stderr, "[tsg seg] %.1f MB %u files: wall to results %.3f ms (K1 %.3f, K2 %.3f, K2 grid %u+%u), "
-                     "copy-out %.3f ms, total %.3f ms\n", total / 1e6, in.nfiles, t_k1_sync, k1, k2, nregions * nsub,
-                     osub, ms_since(t_d2h), ms_since(t_seg0));
-      st->candidates += c2;
+      if (ncands > ln.cand_cap) { ln.cand_cap = static_cast<size_t>(ncands) * 5 / 4 + 1024; continue; }
+      seg_hand_off(r, ncands, nover, defer_copy, out);
 #ifdef TSG_K1_PROBE
-      if (k2_abl_ & kK2Trace) {
-        // probe builds: K2's per-wave stamps appended to $TSG_K2_TRACE_FILE as
-        // [waves, 0, 0, 0][8 x waves] uint32
-        const size_t waves = static_cast<size_t>(k2_grid) * 4;
-        std::vector<uint32_t> tr(4 + 8 * waves, 0);
-        tr[0] = static_cast<uint32_t>(waves);
-        HIP_OK(hipMemcpy(tr.data() + 4, k2_trace, 8 * waves * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        if (const char* fn = std::getenv("TSG_K2_TRACE_FILE")) {
-          if (FILE* fp = std::fopen(fn, "ab")) {
-            std::fwrite(tr.data(), sizeof(uint32_t), tr.size(), fp);
-            std::fclose(fp);
-          }
-        }
-      }
-      if (k1_abl_ & kAblTrace) {
-        // probe builds: the K1 launch's stamps (kAblTrace) appended to
-        // $TSG_K1_TRACE_FILE as [blocks, items, nchunks, chunk][4 x blocks][kTraceItemWords x items] uint32
-        const uint32_t items = static_cast<uint32_t>(std::min<uint64_t>(kTraceItemCap, 3 * (nchunks + 63) / 64 + 64));
-        std::vector<uint32_t> tr(4 + 4 * static_cast<size_t>(blocks) + kTraceItemWords * static_cast<size_t>(items), 0);
-        tr[0] = blocks; tr[1] = items; tr[2] = static_cast<uint32_t>(nchunks); tr[3] = kChunk;
-        HIP_OK(hipMemcpy(tr.data() + 4, ln.d_ob + static_cast<size_t>(blocks) * nthr * kOutSlots,
-                         (tr.size() - 4) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        if (const char* fn = std::getenv("TSG_K1_TRACE_FILE")) {
-          if (FILE* fp = std::fopen(fn, "ab")) {
-            std::fwrite(tr.data(), sizeof(uint32_t), tr.size(), fp);
-            std::fclose(fp);
-          }
-        }
-        HIP_OK(hipMemset(ln.d_ob + static_cast<size_t>(blocks) * nthr * kOutSlots, 0, (tr.size() - 4) * sizeof(uint32_t)));
-      }
+      if (!seg_write_traces(r, err)) return false;
 #endif
-      if (ln.d_k2s) {
-        std::vector<unsigned long long> h(kK2Stat * pf_.rules.size());
-        HIP_OK(hipMemcpy(h.data(), ln.d_k2s, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        HIP_OK(hipMemset(ln.d_k2s, 0, h.size() * sizeof(unsigned long long)));
-        std::lock_guard<std::mutex> lk(k2s_mu_);
-        if (k2s_.size() < h.size()) k2s_.resize(h.size(), 0);
-        for (size_t i = 0; i < h.size(); ++i)
-          k2s_[i] = i % kK2Stat == 4 ? std::max(k2s_[i], h[i]) : k2s_[i] + h[i];
-      }
-      return true;
+      return !ln.d_k2s.p || fold_k2_stats(ln, err);
     }
     if (rerun_k1) continue;
     *err = "candidate buffer overflow persisted";
@@ -2522,6 +2607,7 @@ constexpr size_t kWireCopiesAhead = 3;
 void wire_unpack_launch(const uint8_t* land, uint32_t tab_bytes, uint8_t* dst, uint32_t n, hipStream_t stream);
 
 struct WireFeed {
+  Engine* eng = nullptr;
   struct Seg { const uint8_t* src; uint64_t bytes; const uint64_t* offsets; uint32_t nfiles; };
   std::vector<Seg> segs;               // in upload order; segment i goes to ring[i & 1]
   Lane* ln = nullptr;
@@ -2567,6 +2653,27 @@ struct WireFeed {
     for (size_t i = 0; i < ready.size(); ++i)
       if (slots[ready[i]].seg == seg) return static_cast<int>(i);
     return -1;
+  }
+  // Takes the engine's packers for one scan, hands them its segments and
+  // starts the feeder: *out is set from the moment the packers are held (wind_down()
+  // returns them), and stays null when another scan has them -- that scan
+  // uploads its segments itself, as without wire packing.
+  static bool start(Engine& eng, Lane* ln, int device, const std::vector<Segment>& segs, std::unique_ptr<WireFeed>* out,
+                    std::string* err);
+  // Ends the feeder, parks the packers and gives them back (nothing reads the
+  // caller's data afterwards); the feed's counters go to *st.
+  void wind_down(ScanStats* st);
+  // driver: waits until the feeder has recorded segment si's up_done event
+  bool wait_recorded(size_t si, std::string* e) {
+    std::unique_lock<std::mutex> lk(mu);
+    cv.wait(lk, [&] { return failed || segs_recorded > si; });
+    if (failed) *e = err;
+    return !failed;
+  }
+  // driver: a segment's kernels have finished, its ring slot may be written again
+  void segment_done() {
+    { std::lock_guard<std::mutex> lk(mu); ++segs_done; }
+    cv.notify_all();
   }
   void pack_loop();
   void feed_loop();
@@ -2636,8 +2743,8 @@ bool WireFeed::feed_segment(size_t si, std::string* err) {
   HIP_OK(hipEventRecord(ln->up_begin[slot], ln->copy));
   // (the slot's offsets staging was last read by the upload two segments
   // back, complete since that segment's kernels waited on it)
-  std::memcpy(ln->h_off_pin[slot], sg.offsets, (sg.nfiles + 1) * sizeof(uint64_t));
-  HIP_OK(hipMemcpyAsync(ln->off_slot[slot], ln->h_off_pin[slot], (sg.nfiles + 1) * sizeof(uint64_t),
+  std::memcpy(ln->h_off_pin[slot].p, sg.offsets, (sg.nfiles + 1) * sizeof(uint64_t));
+  HIP_OK(hipMemcpyAsync(ln->off_slot[slot].p, ln->h_off_pin[slot].p, (sg.nfiles + 1) * sizeof(uint64_t),
                         hipMemcpyHostToDevice, ln->copy));
   const uint32_t ns = static_cast<uint32_t>((sg.bytes + strip - 1) / strip);
   {
@@ -2688,7 +2795,7 @@ bool WireFeed::feed_segment(size_t si, std::string* err) {
       cv.notify_all();
     }
     if (id < 0) {
-      HIP_OK(hipMemcpyAsync(ln->ring[slot] + o, sg.src + o, n, hipMemcpyHostToDevice, ln->copy));
+      HIP_OK(hipMemcpyAsync(ln->ring[slot].p + o, sg.src + o, n, hipMemcpyHostToDevice, ln->copy));
       hipEvent_t ev = ln->wire_raw_ev[raw_i++ & 3];
       HIP_OK(hipEventRecord(ev, ln->copy));
       copies.push_back({ev, -1});
@@ -2699,7 +2806,7 @@ bool WireFeed::feed_segment(size_t si, std::string* err) {
       HIP_OK(hipMemcpyAsync(w.d, w.h, wire_len, hipMemcpyHostToDevice, ln->copy));
       HIP_OK(hipEventRecord(w.copied, ln->copy));
       HIP_OK(hipStreamWaitEvent(ln->unpack, w.copied, 0));
-      wire_unpack_launch(w.d, static_cast<uint32_t>(wire_table_bytes(n)), ln->ring[slot] + o, static_cast<uint32_t>(n),
+      wire_unpack_launch(w.d, static_cast<uint32_t>(wire_table_bytes(n)), ln->ring[slot].p + o, static_cast<uint32_t>(n),
                          ln->unpack);
       HIP_OK(hipGetLastError());
       HIP_OK(hipEventRecord(w.unpacked, ln->unpack));
@@ -2710,7 +2817,7 @@ bool WireFeed::feed_segment(size_t si, std::string* err) {
     }
     ++issued;
   }
-  HIP_OK(hipMemsetAsync(ln->ring[slot] + sg.bytes, 0, 64, ln->copy));   // K1 reads 16-B words past the end
+  HIP_OK(hipMemsetAsync(ln->ring[slot].p + sg.bytes, 0, 64, ln->copy));   // K1 reads 16-B words past the end
   HIP_OK(hipEventRecord(ln->wire_copies_done[slot], ln->copy));
   HIP_OK(hipStreamWaitEvent(ln->unpack, ln->wire_copies_done[slot], 0));
   HIP_OK(hipEventRecord(ln->up_done[slot], ln->unpack));
@@ -2763,6 +2870,61 @@ void WireFeed::feed_loop() {
   cv.notify_all();
 }
 
+bool WireFeed::start(Engine& eng, Lane* ln, int device, const std::vector<Segment>& segs,
+                     std::unique_ptr<WireFeed>* out, std::string* err) {
+  const int nt = eng.threads_ > 0 ? eng.threads_ : static_cast<int>(std::min(16u, std::max(1u, std::thread::hardware_concurrency())));
+  const int np = eng.wire_threads_n_ >= 0 ? eng.wire_threads_n_ : std::max(0, std::min(16, nt - 2));
+  const size_t nslots = np > 0 ? static_cast<size_t>(np) + kWireCopiesAhead : 0;
+  std::unique_ptr<WireFeed> f(new WireFeed());
+  f->eng = &eng;
+  f->ln = ln;
+  f->device = device;
+  f->strip = eng.wire_strip_;
+  f->force = eng.wire_mode_ == 2;
+  f->npackers = np;
+  f->timeline = eng.host_profile_;
+  f->slots.resize(nslots);
+  f->nfree = static_cast<int>(nslots);
+  for (const Segment& sg : segs) {
+    f->segs.push_back({sg.in.h_data, sg.bytes, sg.in.offsets, sg.in.nfiles});
+    f->span.push_back({0, static_cast<uint32_t>((sg.bytes + f->strip - 1) / f->strip)});
+  }
+  {
+    std::lock_guard<std::mutex> lk(eng.wire_mu_);
+    if (eng.wire_busy_) return true;
+    eng.wire_busy_ = true;
+  }
+  *out = std::move(f);
+  WireFeed* w = out->get();
+  if (!ln->ensure_wire(nslots, wire_table_bytes(w->strip) + wire_bound(w->strip), err)) return false;
+  {
+    std::lock_guard<std::mutex> lk(eng.wire_mu_);
+    while (static_cast<int>(eng.wire_threads_.size()) < np) eng.wire_threads_.emplace_back([e = &eng] { e->wire_packer_main(); });
+    eng.wire_job_ = w;
+    ++eng.wire_gen_;
+  }
+  eng.wire_cv_.notify_all();
+  w->feeder = std::thread([w] { w->feed_loop(); });
+  return true;
+}
+
+void WireFeed::wind_down(ScanStats* st) {
+  { std::lock_guard<std::mutex> lk(mu); stop = true; }
+  cv.notify_all();
+  if (feeder.joinable()) feeder.join();
+  {
+    std::unique_lock<std::mutex> lk(eng->wire_mu_);
+    eng->wire_job_ = nullptr;
+    eng->wire_cv_.wait(lk, [&] { return eng->wire_active_ == 0; });
+    eng->wire_busy_ = false;
+  }
+  if (timeline) std::fprintf(stderr, "[tsg tl] wire: %d packers busy %.3f ms in all\n", npackers, pack_ms);
+  st->wire_bytes += wire_bytes;
+  st->packed_strips += packed;
+  st->raw_strips += raw;
+  st->pack_ms += pack_ms;
+}
+
 void Engine::wire_packer_main() {
   uint64_t seen = 0;
   std::unique_lock<std::mutex> lk(wire_mu_);
@@ -2785,13 +2947,13 @@ bool Engine::feed_probe(const uint8_t* h_data, uint64_t bytes, double* ms, std::
   Lane* ln = acquire_lane(dt, err);
   if (!ln) return false;
   bool ok = hipSetDevice(dt.device) == hipSuccess;
-  const uint64_t seg = std::min<uint64_t>(segment_, std::max<uint64_t>(bytes, 1));
-  for (int i = 0; i < 2 && ok; ++i) ok = ensure(&ln->ring[i], &ln->ring_cap[i], seg + 64, err);
+  const uint64_t seg = std::min<uint64_t>(seg_.segment, std::max<uint64_t>(bytes, 1));
+  for (int i = 0; i < 2 && ok; ++i) ok = ln->ring[i].ensure(seg + 64, err);
   auto t0 = std::chrono::steady_clock::now();
   int slot = 0;
   for (uint64_t o = 0; ok && o < bytes; o += seg, slot ^= 1) {
     const uint64_t n = std::min(seg, bytes - o);
-    ok = hipMemcpyAsync(ln->ring[slot], h_data + o, n, hipMemcpyHostToDevice, ln->copy) == hipSuccess;
+    ok = hipMemcpyAsync(ln->ring[slot].p, h_data + o, n, hipMemcpyHostToDevice, ln->copy) == hipSuccess;
   }
   ok = ok && hipStreamSynchronize(ln->copy) == hipSuccess;
   *ms = ms_since(t0);
@@ -2828,13 +2990,13 @@ bool Engine::strip_cr(const void* d_src, const uint64_t* d_off, uint32_t nfiles,
     *err = "CR strip: offsets must run from 0 to the batch size";
     ok = false;
   }
-  ok = ok && ensure(&ln->d_cr, &ln->d_cr_cap, cr_strip_scratch_bytes(total), err);
+  ok = ok && ln->d_cr.ensure(cr_strip_scratch_bytes(total), err);
   ok = ok && hipEventRecord(ln->ev[0], ln->compute) == hipSuccess;
   ok = ok && cr_strip_launch(static_cast<const uint8_t*>(d_src), d_off, nfiles, total, static_cast<uint8_t*>(d_dst),
-                             d_new_off, ln->d_cr, ln->compute, err);
+                             d_new_off, ln->d_cr.p, ln->compute, err);
   ok = ok && hipEventRecord(ln->ev[1], ln->compute) == hipSuccess;
   uint64_t stripped = 0;
-  ok = ok && hipMemcpyAsync(&stripped, ln->d_cr, 8, hipMemcpyDeviceToHost, ln->compute) == hipSuccess &&
+  ok = ok && hipMemcpyAsync(&stripped, ln->d_cr.p, 8, hipMemcpyDeviceToHost, ln->compute) == hipSuccess &&
        hipStreamSynchronize(ln->compute) == hipSuccess;
   float kms = 0;
   if (ok && ms) ok = hipEventElapsedTime(&kms, ln->ev[0], ln->ev[1]) == hipSuccess;
@@ -3092,19 +3254,234 @@ void Engine::confirm_segment(CallCtx& cc, const Segment& sg, GpuOut& g, Secret* 
   *nfind_out += nfind.load();
 }
 
+struct ScanJob {
+  size_t seg = 0;
+  GpuOut out;
+};
+
+// What the device drivers of one scan() share.
+struct ScanCall {
+  Engine& eng;
+  const std::vector<Segment>& segs;
+  const std::vector<DeviceTables*>& drivers;
+  // the segment counter, the job queue and the driver fan-out (pipeline.h;
+  // its failure behaviour is tested on simulated devices by
+  // tsg_test_multi_driver_model)
+  DriverPipeline<ScanJob>& pipe;
+  ScanStats* st;
+  bool resident = false;
+  bool dual = false;                   // resident batches of several pieces: two drivers on the device (K1Chain)
+  K1Chain chain;
+  const uint8_t* h_dev = nullptr;      // a direct batch: the device view of its pinned bytes
+  bool wire_want = false;
+  uint64_t max_seg = 0;
+  size_t max_seg_files = 0;
+  std::chrono::steady_clock::time_point t_feed0 = std::chrono::steady_clock::now();
+  std::atomic<int64_t> feed_end_ns{0};
+  std::atomic<bool> confirmer_idle{true};
+  std::mutex st_mu;                    // guards *st and gpu_busy
+  double gpu_busy = 0;
+  bool direct() const { return h_dev != nullptr; }
+};
+
+// One device driver of a scan: takes a lane, feeds the device its segments
+// (the next one's upload behind the current one's kernels) and hands each
+// finished segment to the confirming thread.
+struct SegmentDriver {
+  ScanCall& sc;
+  Engine& eng;
+  DeviceTables* dt;
+  Lane* ln = nullptr;
+  std::string e;
+  ScanStats dst;
+  std::unique_ptr<WireFeed> wf;        // (set: this scan holds the engine's packers)
+  // a finished segment is handed to the confirmer once this thread has
+  // queued the next segment's kernels and planned its confirmation
+  // (plan_confirm) while they run: the confirming pool never waits on the
+  // plan of a segment whose successor is on the GPU
+  // (an idle confirmer gets the segment at once and plans it itself)
+  std::unique_ptr<ScanJob> pending;
+  const std::function<void()> plan_fn{[this] { plan_pending(); }};
+
+  SegmentDriver(ScanCall& c, int di) : sc(c), eng(c.eng), dt(c.drivers[di]) {}
+
+  void plan_pending() {
+    if (!pending) return;
+    pending->out.finish_copy();
+    if (!sc.confirmer_idle.load(std::memory_order_acquire)) eng.plan_confirm(sc.segs[pending->seg], &pending->out);
+    sc.pipe.queue().push(std::move(pending));
+  }
+
+  // the lane's two-slot upload ring, sized for the call's largest segment
+  bool setup_ring() {
+    for (int i = 0; i < 2; ++i) {
+      if (!ln->ring[i].ensure(sc.max_seg + 64, &e) || !ln->off_slot[i].ensure(sc.max_seg_files + 1, &e)) return false;
+      if (!ln->h_off_pin[i].ensure_offsets(sc.max_seg_files, &e)) { e = "pinned offsets staging"; return false; }
+    }
+    return true;
+  }
+
+  // upload of segment `si` into ring slot `slot` (copy stream)
+  bool upload(size_t si, int slot) {
+    if (wf) return true;               // (the feeder uploads the segments in order)
+    const Segment& sg = sc.segs[si];
+    std::string* err = &e;
+    const size_t nb = (sg.in.nfiles + 1) * sizeof(uint64_t);
+    HIP_OK(hipEventRecord(ln->up_begin[slot], ln->copy));
+    // the slot's staging was last read by the upload two segments back,
+    // complete since that segment's kernels waited on it
+    std::memcpy(ln->h_off_pin[slot].p, sg.in.offsets, nb);
+    HIP_OK(hipMemcpyAsync(ln->off_slot[slot].p, ln->h_off_pin[slot].p, nb, hipMemcpyHostToDevice, ln->copy));
+    HIP_OK(hipMemcpyAsync(ln->ring[slot].p, sg.in.h_data, sg.bytes, hipMemcpyHostToDevice, ln->copy));
+    HIP_OK(hipMemsetAsync(ln->ring[slot].p + sg.bytes, 0, 64, ln->copy));   // K1 reads 16-B words past the end
+    HIP_OK(hipEventRecord(ln->up_done[slot], ln->copy));
+    return true;
+  }
+
+  // one small pinned batch: the segment prologue copies it (StageIn)
+  bool stage_direct(const Segment& sg, int slot, StageIn* stage) {
+    const size_t nb = (sg.in.nfiles + 1) * sizeof(uint64_t);
+    std::memcpy(ln->h_off_pin[slot].p, sg.in.offsets, nb);
+    if (!ln->h_off_pin[slot].d) { e = "pinned offsets staging has no device view"; return false; }
+    stage->src = sc.h_dev + sg.b0;
+    stage->dst = ln->ring[slot].p;
+    stage->bytes = sg.bytes;
+    stage->off_src = static_cast<const uint8_t*>(ln->h_off_pin[slot].d);
+    stage->off_dst = reinterpret_cast<uint8_t*>(ln->off_slot[slot].p);
+    stage->off_bytes = nb;
+    return true;
+  }
+
+  // the compute stream waits for segment `cur`'s upload into `slot`
+  bool wait_upload(size_t cur, int slot) {
+    if (wf && !wf->wait_recorded(cur, &e)) return false;
+    std::string* err = &e;
+    HIP_OK(hipStreamWaitEvent(ln->compute, ln->up_done[slot], 0));
+    return true;
+  }
+
+  // segment `cur`, whose bytes are resident or on their way into `slot`:
+  // its passes, then the hand-over of the segment before it
+  bool step(size_t cur, int slot) {
+    const Segment& sg = sc.segs[cur];
+    const bool resident = sc.resident, direct = sc.direct();
+    StageIn stage;                     // (direct batches: this segment's prologue copies)
+    if (direct ? !stage_direct(sg, slot, &stage) : !resident && !wait_upload(cur, slot)) return false;
+    std::unique_ptr<ScanJob> job(new ScanJob());
+    job->seg = cur;
+    ScanStats sst;
+    const double h_start = ms_since(sc.t_feed0);
+    if (!eng.run_segment(*dt, *ln, sg, resident ? sg.in.d_data : ln->ring[slot].p,
+                         resident ? nullptr : ln->off_slot[slot].p, &sst, &job->out, &e, &plan_fn,
+                         sc.dual ? &sc.chain : nullptr, /*defer_copy=*/true, direct ? &stage : nullptr))
+      return false;
+    if (wf) wf->segment_done();        // this segment's ring slot may be written again
+    else if (!resident) sst.wire_bytes += sg.bytes;
+    plan_pending();                    // (a rerun path may not have called it)
+    if (eng.host_profile_) {
+      // GPU timeline of this segment from the scan's anchor event
+      float ub = 0, ud = 0, k1a = 0, k1b = 0, k2b = 0;
+      if (!resident && !direct) {
+        hipEventElapsedTime(&ub, ln->anchor, ln->up_begin[slot]);
+        hipEventElapsedTime(&ud, ln->anchor, ln->up_done[slot]);
+      }
+      hipEventElapsedTime(&k1a, ln->anchor, ln->ev[0]);
+      hipEventElapsedTime(&k1b, ln->anchor, ln->ev[1]);
+      hipEventElapsedTime(&k2b, ln->anchor, ln->ev[3]);
+      std::fprintf(stderr, "[tsg tl] seg %zu: host %.3f-%.3f ms; gpu upload %.3f-%.3f, K1 %.3f-%.3f, K2 done %.3f\n",
+                   cur, h_start, ms_since(sc.t_feed0), ub, ud, k1a, k1b, k2b);
+    }
+    if (!resident && !direct) {
+      float h2d = 0;
+      if (hipEventElapsedTime(&h2d, ln->up_begin[slot], ln->up_done[slot]) == hipSuccess) sst.h2d_ms += h2d;
+      const int64_t ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - sc.t_feed0).count();
+      int64_t prev = sc.feed_end_ns.load();
+      while (ns > prev && !sc.feed_end_ns.compare_exchange_weak(prev, ns)) {}
+    }
+    add_stats(&dst, sst);
+    pending = std::move(job);
+    return true;
+  }
+
+  bool drive() {
+    const size_t nseg = sc.segs.size();
+    const bool resident = sc.resident;
+    ln = eng.acquire_lane(*dt, &e);
+    if (!ln) return false;
+    ln->pool_idle = &sc.confirmer_idle;
+    if (hipSetDevice(dt->device) != hipSuccess) { e = "hipSetDevice failed"; return false; }
+    if (!resident && !setup_ring()) return false;
+    size_t cur = sc.pipe.next_segment();
+    int slot = 0;
+    if (eng.host_profile_) hipEventRecord(ln->anchor, resident ? ln->compute : ln->copy);
+    // one scan at a time has the packers; a concurrent one uploads as before
+    if (sc.wire_want && !WireFeed::start(eng, ln, dt->device, sc.segs, &wf, &e)) return false;
+    if (cur < nseg && !resident && !sc.direct() && !upload(cur, slot)) return false;
+    while (cur < nseg && !sc.pipe.queue().aborted()) {
+      // (resident data: the next segment is taken when this one is done, so
+      // two drivers take them in order)
+      const size_t nxt = resident ? nseg : sc.pipe.next_segment();
+      // the next segment's upload goes behind this one's on the copy stream;
+      // its ring slot was last read by the segment before this one, whose
+      // kernels have completed (run_segment returns after its D2H)
+      if (nxt < nseg && !resident && !upload(nxt, slot ^ 1)) return false;
+      if (!step(cur, slot)) return false;
+      cur = resident ? sc.pipe.next_segment() : nxt;
+      slot ^= 1;
+    }
+    plan_pending();
+    return true;
+  }
+
+  // always runs: the feeder and the packers stop and are parked before the
+  // call returns (nothing reads the caller's data after it), a failed
+  // driver's streams are drained, the lane goes back
+  void teardown(bool ok, std::chrono::steady_clock::time_point tb) {
+    if (wf) wf->wind_down(&dst);
+    if (ln) {
+      if (!ok) { hipStreamSynchronize(ln->copy); hipStreamSynchronize(ln->compute); if (ln->unpack) hipStreamSynchronize(ln->unpack); }
+      ln->pool_idle = nullptr;                   // (the flag is this scan's)
+      eng.release_lane(*dt, ln);
+    }
+    std::lock_guard<std::mutex> lk(sc.st_mu);
+    add_stats(sc.st, dst);
+    sc.gpu_busy = sc.dual ? std::max(sc.gpu_busy, ms_since(tb)) : sc.gpu_busy + ms_since(tb);
+  }
+
+  bool run(std::string* e_out) {
+    const auto tb = std::chrono::steady_clock::now();
+    bool ok = false;
+    // (a host exception -- bad_alloc of a plan or a copy-out -- ends this
+    // driver like a HIP error: the queue is aborted and the call fails; it
+    // must not escape the thread)
+    try {
+      ok = drive();
+    } catch (const std::exception& x) {
+      ok = false;
+      e = std::string("host exception in the device driver: ") + x.what();
+    } catch (...) {
+      ok = false;
+      e = "host exception in the device driver";
+    }
+    teardown(ok, tb);
+    if (!ok) *e_out = e;
+    return ok;
+  }
+};
+
 // One batch through the pipeline:
 //  * uploaded data (h_data only): the batch is cut into segments of about
-//    segment_ bytes at file boundaries; each device's driver thread takes
-//    segments from a shared queue, uploads the next one on its copy stream
-//    while K1/K2 of the current one run on its compute stream (two-slot
-//    upload ring), and hands each finished segment to this thread, which
-//    confirms it on the host while the drivers go on;
+//    the policy's segment bytes at file boundaries; each device's driver
+//    thread takes segments from a shared queue, uploads the next one on its
+//    copy stream while K1/K2 of the current one run on its compute stream
+//    (two-slot upload ring), and hands each finished segment to this thread,
+//    which confirms it on the host while the drivers go on;
 //  * resident data (d_data on one of the engine's devices): pieces (TSG_PIECES,
-//    the first taking first_piece_ of the bytes), GPU passes of piece i+1 on
+//    the first taking first_piece of the bytes), GPU passes of piece i+1 on
 //    the driver while this thread confirms piece i.
 // Every segment is a self-contained batch (offsets rebased to 0, data a
-// 16-byte aligned sub-range), so the kernels are unchanged and the result is
-// the one-segment result.
+// 16-byte aligned sub-range; segments.h), so the kernels are unchanged and the
+// result is the one-segment result.
 bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::string* err) {
   ScanStats local;
   if (!st) st = &local;
@@ -3130,418 +3507,39 @@ bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::
     st->total_ms = ms_since(t0);
     return true;
   }
-  // --- segments
-  std::vector<Segment> segs;
-  std::vector<DeviceTables*> drivers;
+  // --- segments and the devices that drive them
   const bool resident = in.d_data != nullptr;
-  {
-    std::vector<uint32_t> cut{0};
-    if (resident) {
-      const int dev = device_of(in.d_data);
-      for (auto& d : dev_) if (d->device == dev) { drivers.push_back(d.get()); break; }
-      if (drivers.empty()) { *err = "d_data is not device memory of one of the engine's devices"; return false; }
-      const uint32_t want = static_cast<uint32_t>(std::min<uint64_t>(pieces_, std::max<uint64_t>(1, total / min_piece_)));
-      // piece 0 takes first_piece_ of the bytes; with last_piece_ a short
-      // last piece of that share follows the others (its confirmation is the
-      // tail left after the GPU's last pass); the rest share what remains
-      const bool short_last = last_piece_ > 0.0 && want >= 5;
-      // batches of 3 pieces (0.75-1 GB) start with a larger piece
-      // (TSG_FIRST_PIECE_FEW; 1 GB of config-1 files: 1.49-1.50 ms per step
-      // at 10%, 1.43-1.46 at 20%, 1.45-1.46 at 30%, profiles/r8d_*)
-      const double first = want == 3 ? first_piece_few_ : first_piece_;
-      const double mid = 1.0 - first - (short_last ? last_piece_ : 0.0);
-      const uint32_t nmid = want - 1 - (short_last ? 1 : 0);
-      for (uint32_t p = 1; p < want; ++p) {
-        const double share = p <= nmid ? first + mid * (p - 1) / nmid : 1.0 - last_piece_;
-        const uint64_t target = static_cast<uint64_t>(share * static_cast<double>(total));
-        const uint32_t f = static_cast<uint32_t>(std::lower_bound(in.offsets, in.offsets + in.nfiles, target) - in.offsets);
-        if (f > cut.back() && f < in.nfiles) cut.push_back(f);
-      }
-    } else {
-      // Geometric tail: the work left after the last upload is the last
-      // segment's K1/K2 and host confirmation.  For batches whose confirm
-      // cost per byte is high (many small files: image layers, config 5) or
-      // that are too small for several full segments, the rest after the full
-      // segments is cut in halves down to segment_min_, so the last segment
-      // is small and every upload overlaps the previous segment's work.
-      // Large-file batches keep full segments (K1 runs at its large-launch
-      // rate and their confirmation is cheap).
-      const bool dense = static_cast<double>(in.nfiles) * 1e9 > kDenseFilesPerGB * static_cast<double>(total);
-      const bool geometric = dense || total < 2 * segment_;
-      for (uint32_t f = 0; f < in.nfiles;) {
-        // next cut: the first file boundary at or past segment_ bytes from
-        // here; optionally (segment_tail_ > 0) the batch ends in a short
-        // segment, so the kernels and confirmation left after the last upload
-        // are shorter (measured: ~1 ms of a 179 ms 10 GB step, while the
-        // short launch runs K1 at ~2.1 TB/s against 3 TB/s for 4 GB)
-        const uint64_t rest = total - in.offsets[f];
-        const uint64_t tail = std::min(segment_tail_, segment_ / 8);
-        uint64_t target;
-        // (geometric batches start halving once less than two full segments
-        // are left: a full segment's confirmation then hides behind the next
-        // half-size upload; r3t config 5: 4.3+4.3+0.7+... GB left 16 ms after
-        // the last upload, the second segment's 25 ms confirmation)
-        // (large-file batches: the rest is cut into ceil(rest / segment_)
-        // equal segments instead of full segments plus a short remainder, so
-        // every K1 launch runs at its large-launch rate: a 10 GB batch is
-        // 3 x 3.33 GB, not 4 + 4 + 1.4 GB whose last launch ran at ~2.3 TB/s;
-        // TSG_SEGMENT_BALANCED=0 keeps full segments)
-        const uint64_t kleft = (rest + segment_ - 1) / segment_;
-        if (!geometric && balanced_ && tail == 0 && kleft >= 2) target = in.offsets[f] + rest / kleft;
-        else if (geometric ? rest >= 2 * segment_ : rest > segment_ + tail) target = in.offsets[f] + segment_;
-        else if (geometric && rest / 2 >= segment_min_) target = in.offsets[f] + rest / 2;
-        else if (tail > 0 && rest > 2 * tail) target = total - tail;
-        else break;
-        uint32_t g = static_cast<uint32_t>(std::lower_bound(in.offsets + f, in.offsets + in.nfiles, target) - in.offsets);
-        if (g <= f) g = f + 1;
-        if (g >= in.nfiles) break;
-        cut.push_back(g);
-        f = g;
-      }
-      const size_t nseg = cut.size();
-      for (auto& d : dev_) {
-        if (drivers.size() >= nseg) break;
-        drivers.push_back(d.get());
-      }
-    }
-    cut.push_back(in.nfiles);
-    segs.resize(cut.size() - 1);
-    for (size_t p = 0; p < segs.size(); ++p) {
-      const uint32_t a = cut[p], b = cut[p + 1];
-      Segment& sg = segs[p];
-      BatchInput& q = sg.in;
-      q = in;
-      sg.f0 = a;
-      sg.b0 = in.offsets[a];
-      sg.bytes = in.offsets[b] - in.offsets[a];
-      if (segs.size() > 1) {
-        sg.off.resize(b - a + 1);
-        for (uint32_t f = a; f <= b; ++f) sg.off[f - a] = in.offsets[f] - sg.b0;
-        q.offsets = sg.off.data();
-      }
-      q.nfiles = b - a;
-      q.h_data = in.h_data ? in.h_data + sg.b0 : nullptr;
-      q.d_data = resident ? static_cast<const uint8_t*>(in.d_data) + sg.b0 : nullptr;
-      q.paths = in.paths ? in.paths + a : nullptr;
-      q.path_lens = in.path_lens ? in.path_lens + a : nullptr;
-      q.binary = in.binary ? in.binary + a : nullptr;
-      // a resident piece after the first starts at an arbitrary file offset:
-      // K1 reads 64-byte lines from the piece's base, and a base off the
-      // 128-byte L2 line grid made it fetch 2.4 HBM bytes per content byte
-      // (aligned pieces 1.5, profiles/rd4k traffic runs).  Start it at the
-      // 256-byte boundary below, the bytes in between a lead file.
-      const uint64_t delta = resident && p > 0 ? (reinterpret_cast<uintptr_t>(in.d_data) + sg.b0) & 255u : 0;
-      if (delta && in.h_data && in.paths) {
-        sg.lead = 1;
-        sg.off.insert(sg.off.begin(), 0);
-        for (size_t k = 1; k < sg.off.size(); ++k) sg.off[k] += delta;
-        q.offsets = sg.off.data();
-        q.nfiles = b - a + 1;
-        q.h_data -= delta;
-        q.d_data = static_cast<const uint8_t*>(q.d_data) - delta;
-        sg.lead_paths.assign(1, "");
-        sg.lead_paths.insert(sg.lead_paths.end(), in.paths + a, in.paths + b);
-        q.paths = sg.lead_paths.data();
-        if (in.path_lens) {
-          sg.lead_lens.assign(1, 0);
-          sg.lead_lens.insert(sg.lead_lens.end(), in.path_lens + a, in.path_lens + b);
-          q.path_lens = sg.lead_lens.data();
-        }
-        if (in.binary) {
-          sg.lead_bin.assign(1, 0);
-          sg.lead_bin.insert(sg.lead_bin.end(), in.binary + a, in.binary + b);
-          q.binary = sg.lead_bin.data();
-        }
-      }
-    }
+  std::vector<DeviceTables*> drivers;
+  if (resident) {
+    const int dev = device_of(in.d_data);
+    for (auto& d : dev_) if (d->device == dev) { drivers.push_back(d.get()); break; }
+    if (drivers.empty()) { *err = "d_data is not device memory of one of the engine's devices"; return false; }
   }
-  // resident batches of several pieces: two drivers on the device (K1Chain)
+  std::vector<Segment> segs;
+  plan_segments(in, resident, seg_, &segs);
+  for (auto& d : dev_) {
+    if (resident || drivers.size() >= segs.size()) break;
+    drivers.push_back(d.get());
+  }
   const bool dual = resident && segs.size() >= 2 && resident_drivers_ >= 2;
-  K1Chain chain;
-  K1Chain* chain_p = dual ? &chain : nullptr;
   if (dual) drivers.push_back(drivers[0]);
-  uint64_t max_seg = 0;
-  size_t max_seg_files = 0;
+  DriverPipeline<ScanJob> pipe(static_cast<int>(drivers.size()), segs.size());
+  ScanCall sc{*this, segs, drivers, pipe, st};
+  sc.resident = resident;
+  sc.dual = dual;
   for (const Segment& sg : segs) {
-    max_seg = std::max(max_seg, sg.bytes);
-    max_seg_files = std::max<size_t>(max_seg_files, sg.in.nfiles);
+    sc.max_seg = std::max(sc.max_seg, sg.bytes);
+    sc.max_seg_files = std::max<size_t>(sc.max_seg_files, sg.in.nfiles);
   }
-
-  struct Job {
-    size_t seg = 0;
-    GpuOut out;
-  };
-  // the segment counter, the job queue and the driver fan-out (pipeline.h;
-  // its failure behaviour is tested on simulated devices by
-  // tsg_test_multi_driver_model)
-  DriverPipeline<Job> pipe(static_cast<int>(drivers.size()), segs.size());
-  JobQueue<Job>& q = pipe.queue();
-  std::mutex st_mu;
-  double gpu_busy = 0;
-  auto t_feed0 = std::chrono::steady_clock::now();
-  std::atomic<int64_t> feed_end_ns{0};
-  std::atomic<bool> confirmer_idle{true};
   // a batch small enough for one segment in pinned host memory: staged by the
   // segment prologue over PCIe (tsg_prologue) instead of the copy engine
-  const uint8_t* h_dev = nullptr;
-  if (!resident && segs.size() == 1 && drivers.size() == 1 && total <= kDirectStageBytes && in.h_data) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, in.h_data) == hipSuccess && a.type == hipMemoryTypeHost && a.devicePointer) {
-      // (the attributes may describe the allocation's base: offset the device view likewise)
-      const uint8_t* hp = a.hostPointer ? static_cast<const uint8_t*>(a.hostPointer) : in.h_data;
-      h_dev = static_cast<const uint8_t*>(a.devicePointer) + (in.h_data - hp);
-    } else
-
-      (void)hipGetLastError();
-  }
-  const bool direct = h_dev != nullptr;
+  if (!resident && segs.size() == 1 && drivers.size() == 1 && total <= kDirectStageBytes && in.h_data)
+    sc.h_dev = pinned_device_view(in.h_data);
   // wire packing: uploaded batches of at least four strips on one device,
   // except the dense small-file batches whose bound is host confirmation
   // (the packers would take its CPUs)
-  const bool wire_want = wire_mode_ != 0 && !resident && !direct && in.h_data && drivers.size() == 1 &&
-                         total >= 4 * wire_strip_ &&
-                         !(static_cast<double>(in.nfiles) * 1e9 > kDenseFilesPerGB * static_cast<double>(total));
-  auto driver = [&](int di, std::string* e_out) -> bool {
-    DeviceTables* dt = drivers[di];
-    std::string e;
-    ScanStats dst;
-    auto tb = std::chrono::steady_clock::now();
-    Lane* ln = nullptr;
-    bool ok = false;
-    std::unique_ptr<WireFeed> wf;        // (set: this scan holds the engine's packers)
-    bool wire_held = false;
-    // (a host exception -- bad_alloc of a plan or a copy-out -- ends this
-    // driver like a HIP error: the queue is aborted and the call fails; it
-    // must not escape the thread)
-    try {
-    ln = acquire_lane(*dt, &e);
-    ok = ln != nullptr;
-    if (ok) ln->pool_idle = &confirmer_idle;
-    if (ok && hipSetDevice(dt->device) != hipSuccess) { ok = false; e = "hipSetDevice failed"; }
-    if (ok && !resident) {
-      for (int i = 0; i < 2 && ok; ++i) {
-        ok = ensure(&ln->ring[i], &ln->ring_cap[i], max_seg + 64, &e) &&
-             ensure(&ln->off_slot[i], &ln->off_slot_cap[i], max_seg_files + 1, &e);
-        if (ok && ln->h_off_pin_cap[i] < max_seg_files + 1) {
-          if (ln->h_off_pin[i]) hipHostFree(ln->h_off_pin[i]);
-          ln->h_off_pin[i] = nullptr;
-          ln->h_off_pin_cap[i] = 0;
-          if (hipHostMalloc(reinterpret_cast<void**>(&ln->h_off_pin[i]), (max_seg_files + 1) * sizeof(uint64_t),
-                            hipHostMallocDefault) != hipSuccess) { ok = false; e = "pinned offsets staging"; }
-          else ln->h_off_pin_cap[i] = max_seg_files + 1;
-        }
-      }
-    }
-    // upload of segment `si` into ring slot `slot` (copy stream)
-    auto upload = [&](size_t si, int slot) -> bool {
-      if (wf) return true;               // (the feeder uploads the segments in order)
-      const Segment& sg = segs[si];
-      std::string* err = &e;
-      HIP_OK(hipEventRecord(ln->up_begin[slot], ln->copy));
-      // the slot's staging was last read by the upload two segments back,
-      // complete since that segment's kernels waited on it
-      std::memcpy(ln->h_off_pin[slot], sg.in.offsets, (sg.in.nfiles + 1) * sizeof(uint64_t));
-      HIP_OK(hipMemcpyAsync(ln->off_slot[slot], ln->h_off_pin[slot], (sg.in.nfiles + 1) * sizeof(uint64_t),
-                            hipMemcpyHostToDevice, ln->copy));
-      HIP_OK(hipMemcpyAsync(ln->ring[slot], sg.in.h_data, sg.bytes, hipMemcpyHostToDevice, ln->copy));
-      HIP_OK(hipMemsetAsync(ln->ring[slot] + sg.bytes, 0, 64, ln->copy));   // K1 reads 16-B words past the end
-      HIP_OK(hipEventRecord(ln->up_done[slot], ln->copy));
-      return true;
-    };
-    // a finished segment is handed to the confirmer once this thread has
-    // queued the next segment's kernels and planned its confirmation
-    // (plan_confirm) while they run: the confirming pool never waits on the
-    // plan of a segment whose successor is on the GPU
-    // (an idle confirmer gets the segment at once and plans it itself)
-    std::unique_ptr<Job> pending;
-    const std::function<void()> plan_pending = [&]() {
-      if (!pending) return;
-      pending->out.finish_copy();
-      if (!confirmer_idle.load(std::memory_order_acquire)) plan_confirm(segs[pending->seg], &pending->out);
-      q.push(std::move(pending));
-    };
-    size_t cur = ok ? pipe.next_segment() : segs.size();
-    int slot = 0;
-    if (ok && host_profile_) hipEventRecord(ln->anchor, resident ? ln->compute : ln->copy);
-    if (ok && wire_want) {
-      // one scan at a time has the packers; a concurrent one uploads as before
-      {
-        std::lock_guard<std::mutex> lk(wire_mu_);
-        if (!wire_busy_) wire_busy_ = wire_held = true;
-      }
-      if (wire_held) {
-        const int nt = threads_ > 0 ? threads_ : static_cast<int>(std::min(16u, std::max(1u, std::thread::hardware_concurrency())));
-        const int np = wire_threads_n_ >= 0 ? wire_threads_n_ : std::max(0, std::min(16, nt - 2));
-        const size_t nslots = np > 0 ? static_cast<size_t>(np) + kWireCopiesAhead : 0;
-        const size_t cap = wire_table_bytes(wire_strip_) + wire_bound(wire_strip_);
-        std::string* err = &e;
-        auto setup = [&]() -> bool {
-          if (!ln->unpack) HIP_OK(hipStreamCreateWithFlags(&ln->unpack, hipStreamNonBlocking));
-          const unsigned evf = hipEventBlockingSync | hipEventDisableTiming;
-          for (auto& ev : ln->wire_raw_ev) if (!ev) HIP_OK(hipEventCreateWithFlags(&ev, evf));
-          for (auto& ev : ln->wire_copies_done) if (!ev) HIP_OK(hipEventCreateWithFlags(&ev, evf));
-          if (ln->wire.size() < nslots || ln->wire_cap < cap) {
-            // (pinned staging of this size is far too slow to allocate per call: kept on the lane)
-            ln->free_wire();
-            ln->wire.resize(nslots);
-            ln->wire_cap = cap;
-            for (Lane::WireSlot& w : ln->wire) {
-              HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&w.h), cap, hipHostMallocDefault));
-              HIP_OK(hipMalloc(reinterpret_cast<void**>(&w.d), cap));
-              HIP_OK(hipEventCreateWithFlags(&w.copied, evf));
-              HIP_OK(hipEventCreateWithFlags(&w.unpacked, evf));
-            }
-          }
-          return true;
-        };
-        ok = setup();
-        if (ok) {
-          wf.reset(new WireFeed());
-          wf->ln = ln;
-          wf->device = dt->device;
-          wf->strip = wire_strip_;
-          wf->force = wire_mode_ == 2;
-          wf->npackers = np;
-          wf->timeline = host_profile_;
-          wf->slots.resize(nslots);
-          wf->nfree = static_cast<int>(nslots);
-          for (const Segment& sg : segs) {
-            wf->segs.push_back({sg.in.h_data, sg.bytes, sg.in.offsets, sg.in.nfiles});
-            wf->span.push_back({0, static_cast<uint32_t>((sg.bytes + wire_strip_ - 1) / wire_strip_)});
-          }
-          {
-            std::lock_guard<std::mutex> lk(wire_mu_);
-            while (static_cast<int>(wire_threads_.size()) < np) wire_threads_.emplace_back([this] { wire_packer_main(); });
-            wire_job_ = wf.get();
-            ++wire_gen_;
-          }
-          wire_cv_.notify_all();
-          wf->feeder = std::thread([f = wf.get()] { f->feed_loop(); });
-        }
-      }
-    }
-    if (ok && cur < segs.size() && !resident && !direct) ok = upload(cur, slot);
-    while (ok && cur < segs.size() && !q.aborted()) {
-      // (resident data: the next segment is taken when this one is done, so
-      // two drivers take them in order)
-      const size_t nxt = resident ? segs.size() : pipe.next_segment();
-      // the next segment's upload goes behind this one's on the copy stream;
-      // its ring slot was last read by the segment before this one, whose
-      // kernels have completed (run_segment returns after its D2H)
-      if (nxt < segs.size() && !resident && !(ok = upload(nxt, slot ^ 1))) break;
-      const void* d_data = resident ? segs[cur].in.d_data : ln->ring[slot];
-      StageIn stage;                     // (direct batches: this segment's prologue copies)
-      if (direct) {
-        // one small pinned batch: the segment prologue copies it (StageIn)
-        const Segment& sg = segs[cur];
-        std::memcpy(ln->h_off_pin[slot], sg.in.offsets, (sg.in.nfiles + 1) * sizeof(uint64_t));
-        void* off_dev = nullptr;
-        if (hipHostGetDevicePointer(&off_dev, ln->h_off_pin[slot], 0) != hipSuccess || !off_dev) {
-          ok = false;
-          e = "pinned offsets staging has no device view";
-          break;
-        }
-        stage.src = h_dev + sg.b0;
-        stage.dst = ln->ring[slot];
-        stage.bytes = sg.bytes;
-        stage.off_src = static_cast<const uint8_t*>(off_dev);
-        stage.off_dst = reinterpret_cast<uint8_t*>(ln->off_slot[slot]);
-        stage.off_bytes = (sg.in.nfiles + 1) * sizeof(uint64_t);
-      } else if (!resident) {
-        std::string* err = &e;
-        auto wait_up = [&]() -> bool {
-          HIP_OK(hipStreamWaitEvent(ln->compute, ln->up_done[slot], 0));
-          return true;
-        };
-        if (wf) {
-          // the feeder records up_done[slot] once the segment's last copy is queued
-          std::unique_lock<std::mutex> lk(wf->mu);
-          wf->cv.wait(lk, [&] { return wf->failed || wf->segs_recorded > cur; });
-          if (wf->failed) { ok = false; e = wf->err; break; }
-        }
-        if (!(ok = wait_up())) break;
-      }
-      std::unique_ptr<Job> job(new Job());
-      job->seg = cur;
-      ScanStats sst;
-      const double h_start = ms_since(t_feed0);
-      ok = run_segment(*dt, *ln, segs[cur], d_data, resident ? nullptr : ln->off_slot[slot], &sst, &job->out, &e,
-                       &plan_pending, chain_p, /*defer_copy=*/true, direct ? &stage : nullptr);
-      if (!ok) break;
-      if (wf) {
-        // this segment's ring slot may be written again
-        { std::lock_guard<std::mutex> lk(wf->mu); ++wf->segs_done; }
-        wf->cv.notify_all();
-      } else if (!resident) {
-        sst.wire_bytes += segs[cur].bytes;
-      }
-      plan_pending();                    // (a rerun path may not have called it)
-      if (host_profile_) {
-        // GPU timeline of this segment from the scan's anchor event
-        float ub = 0, ud = 0, k1a = 0, k1b = 0, k2b = 0;
-        if (!resident && !direct) {
-          hipEventElapsedTime(&ub, ln->anchor, ln->up_begin[slot]);
-          hipEventElapsedTime(&ud, ln->anchor, ln->up_done[slot]);
-        }
-        hipEventElapsedTime(&k1a, ln->anchor, ln->ev[0]);
-        hipEventElapsedTime(&k1b, ln->anchor, ln->ev[1]);
-        hipEventElapsedTime(&k2b, ln->anchor, ln->ev[3]);
-        std::fprintf(stderr, "[tsg tl] seg %zu: host %.3f-%.3f ms; gpu upload %.3f-%.3f, K1 %.3f-%.3f, K2 done %.3f\n",
-                     cur, h_start, ms_since(t_feed0), ub, ud, k1a, k1b, k2b);
-      }
-      if (!resident && !direct) {
-        float h2d = 0;
-        if (hipEventElapsedTime(&h2d, ln->up_begin[slot], ln->up_done[slot]) == hipSuccess) sst.h2d_ms += h2d;
-        const int64_t ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_feed0).count();
-        int64_t prev = feed_end_ns.load();
-        while (ns > prev && !feed_end_ns.compare_exchange_weak(prev, ns)) {}
-      }
-      add_stats(&dst, sst);
-      pending = std::move(job);
-      cur = resident ? pipe.next_segment() : nxt;
-      slot ^= 1;
-    }
-    if (ok) plan_pending();
-    } catch (const std::exception& x) {
-      ok = false;
-      e = std::string("host exception in the device driver: ") + x.what();
-    } catch (...) {
-      ok = false;
-      e = "host exception in the device driver";
-    }
-    if (wf) {
-      // the feeder and the packers stop and are parked before the call
-      // returns: nothing reads the caller's data after it
-      { std::lock_guard<std::mutex> lk(wf->mu); wf->stop = true; }
-      wf->cv.notify_all();
-      if (wf->feeder.joinable()) wf->feeder.join();
-    }
-    if (wire_held) {
-      std::unique_lock<std::mutex> lk(wire_mu_);
-      wire_job_ = nullptr;
-      wire_cv_.wait(lk, [&] { return wire_active_ == 0; });
-      wire_busy_ = false;
-    }
-    if (wf) {
-      if (host_profile_) std::fprintf(stderr, "[tsg tl] wire: %d packers busy %.3f ms in all\n", wf->npackers, wf->pack_ms);
-      dst.wire_bytes += wf->wire_bytes;
-      dst.packed_strips += wf->packed;
-      dst.raw_strips += wf->raw;
-      dst.pack_ms += wf->pack_ms;
-    }
-    if (ln) {
-      if (!ok) { hipStreamSynchronize(ln->copy); hipStreamSynchronize(ln->compute); if (ln->unpack) hipStreamSynchronize(ln->unpack); }
-      ln->pool_idle = nullptr;                   // (the flag is this scan's)
-      release_lane(*dt, ln);
-    }
-    {
-      std::lock_guard<std::mutex> lk(st_mu);
-      add_stats(st, dst);
-      gpu_busy = dual ? std::max(gpu_busy, ms_since(tb)) : gpu_busy + ms_since(tb);
-    }
-    if (!ok) *e_out = e;
-    return ok;
-  };
+  sc.wire_want = wire_mode_ != 0 && !resident && !sc.direct() && in.h_data && drivers.size() == 1 &&
+                 total >= 4 * wire_strip_ && !dense_batch(in.nfiles, total, seg_);
   CallCtx* cc = acquire_call();
   uint64_t nconf = 0, nfind = 0;
   double host_ms = 0;
@@ -3551,24 +3549,24 @@ bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::
   const bool inline_driver = segs.size() == 1 && drivers.size() == 1;
   std::string run_err;
   const bool run_ok = pipe.run(
-      inline_driver, driver,
+      inline_driver, [&](int di, std::string* e_out) { return SegmentDriver(sc, di).run(e_out); },
       [&] {
         // per-file result slots (hundreds of thousands for image layers) are set up
         // while the first segment's upload and GPU passes run
         results->clear();
         results->resize(in.nfiles);
-        if (host_profile_) std::fprintf(stderr, "[tsg tl] %u result slots ready at %.3f ms\n", in.nfiles, ms_since(t_feed0));
+        if (host_profile_) std::fprintf(stderr, "[tsg tl] %u result slots ready at %.3f ms\n", in.nfiles, ms_since(sc.t_feed0));
       },
-      [&](Job& job, int left) {
+      [&](ScanJob& job, int left) {
         auto th = std::chrono::steady_clock::now();
         const Segment& sg = segs[job.seg];
-        const double c_start = host_profile_ ? ms_since(t_feed0) : 0.0;
-        confirmer_idle.store(false, std::memory_order_release);
+        const double c_start = host_profile_ ? ms_since(sc.t_feed0) : 0.0;
+        sc.confirmer_idle.store(false, std::memory_order_release);
         // (drivers that block on an event leave every core to the pool)
         confirm_segment(*cc, sg, job.out, results->data() + sg.f0, &nconf, &nfind, left > 0 && !dual);
-        confirmer_idle.store(true, std::memory_order_release);
+        sc.confirmer_idle.store(true, std::memory_order_release);
         host_ms += ms_since(th);
-        if (host_profile_) std::fprintf(stderr, "[tsg tl] seg %zu confirm %.3f-%.3f ms\n", job.seg, c_start, ms_since(t_feed0));
+        if (host_profile_) std::fprintf(stderr, "[tsg tl] seg %zu confirm %.3f-%.3f ms\n", job.seg, c_start, ms_since(sc.t_feed0));
       },
       pop_spin_us_, &run_err);
   release_call(cc);
@@ -3577,11 +3575,11 @@ bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::
   st->files = in.nfiles;
   st->pieces = static_cast<uint32_t>(segs.size());
   st->devices = static_cast<uint32_t>(drivers.size());
-  st->gpu_wall_ms = gpu_busy;
+  st->gpu_wall_ms = sc.gpu_busy;
   st->host_ms = host_ms;
   st->confirm_files = nconf;
   st->findings = nfind;
-  st->feed_ms = resident ? 0.0 : feed_end_ns.load() / 1e6;
+  st->feed_ms = resident ? 0.0 : sc.feed_end_ns.load() / 1e6;
   st->total_ms = ms_since(t0);
   return true;
 }

@@ -1,4 +1,6 @@
-// CPU model of Engine::scan's multi-device segment pipeline (pipeline.h) for
+// CPU models of Engine::scan's host logic for tests without a GPU: the
+// segment planner (segments.h, tsg_test_plan_segments, at the end) and the
+// multi-device segment pipeline (pipeline.h) for
 // tests and sanitizer runs without a GPU: `ndevices` simulated device drivers
 // pull segments from the shared counter, each holding a lane from its
 // device's pool while it runs, and hand finished segments to the confirming
@@ -20,6 +22,7 @@
 #include <vector>
 
 #include "pipeline.h"
+#include "segments.h"
 #include "trivy_secret.h"
 #include "trivy_secret_test.h"
 
@@ -132,6 +135,54 @@ extern "C" int tsg_test_multi_driver_model(uint32_t ndevices, uint32_t nsegments
     return TSG_OK;
   } catch (const std::bad_alloc&) {
     return capi_fail(TSG_ERR_INTERNAL, "out of memory");
+  } catch (const std::exception& x) {
+    return capi_fail(TSG_ERR_INTERNAL, std::string("internal error: ") + x.what());
+  }
+}
+
+extern "C" int tsg_test_plan_segments(const uint64_t* offsets, uint32_t nfiles, int resident, uint64_t base,
+                                      int with_paths, const tsg_segment_policy* pol, tsg_segment_info* out,
+                                      uint32_t out_cap, uint32_t* nout, uint64_t* rebased, size_t rebased_cap) {
+  using namespace tsg;
+  if (!offsets || !pol || !out || !nout || nfiles == 0 || offsets[0] != 0 || offsets[nfiles] == 0)
+    return capi_fail(TSG_ERR_INVALID, "bad argument");
+  for (uint32_t i = 0; i < nfiles; ++i)
+    if (offsets[i + 1] < offsets[i]) return capi_fail(TSG_ERR_INVALID, "offsets must be non-decreasing");
+  try {
+    SegmentPolicy p;
+    p.pieces = pol->pieces;
+    p.first_piece = pol->first_piece;
+    p.first_piece_few = pol->first_piece_few;
+    p.last_piece = pol->last_piece;
+    p.min_piece = pol->min_piece;
+    p.segment = pol->segment;
+    p.segment_min = pol->segment_min;
+    p.balanced = pol->balanced != 0;
+    p.dense_files_per_gb = pol->dense_files_per_gb;
+    // the planner only does address arithmetic on the data pointers: a host
+    // "copy" at an address no lead can underflow, the device one at `base`
+    BatchInput in;
+    in.h_data = reinterpret_cast<const uint8_t*>(uintptr_t(1) << 20);
+    in.d_data = resident ? reinterpret_cast<const void*>(static_cast<uintptr_t>(base)) : nullptr;
+    in.offsets = offsets;
+    in.nfiles = nfiles;
+    std::vector<const char*> paths(with_paths ? nfiles : 0, "");
+    if (with_paths) in.paths = paths.data();
+    std::vector<Segment> segs;
+    plan_segments(in, resident != 0, p, &segs);
+    *nout = static_cast<uint32_t>(segs.size());
+    if (segs.size() > out_cap) return capi_fail(TSG_ERR_INVALID, "more segments than out_cap");
+    size_t r = 0;
+    for (size_t k = 0; k < segs.size(); ++k) {
+      const Segment& sg = segs[k];
+      out[k] = tsg_segment_info{sg.f0, sg.in.nfiles, sg.lead, sg.b0, sg.bytes,
+                                static_cast<uint64_t>(reinterpret_cast<uintptr_t>(sg.in.d_data))};
+      if (!rebased) continue;
+      if (r + sg.in.nfiles + 1 > rebased_cap) return capi_fail(TSG_ERR_INVALID, "rebased_cap too small");
+      std::copy(sg.in.offsets, sg.in.offsets + sg.in.nfiles + 1, rebased + r);
+      r += sg.in.nfiles + 1;
+    }
+    return TSG_OK;
   } catch (const std::exception& x) {
     return capi_fail(TSG_ERR_INTERNAL, std::string("internal error: ") + x.what());
   }
