@@ -25,8 +25,36 @@ int tsg_go_json_string(const uint8_t* s, size_t n, int escape_html, char** out, 
 int tsg_prefilter_resident(tsg_engine* e, const void* d_data, const uint8_t* h_data,
                            const uint64_t* offsets, uint32_t nfiles, tsg_result** out);
 
-/* Raw GPU candidates of file i for rule j (sorted starts); for tests. */
+/* Raw GPU candidates of file i for rule j (sorted starts); for tests.  Rule
+ * indices past tsg_ruleset_num_rules are the exclude-block pseudo-rules, in
+ * the order of the prefilter report. */
 int tsg_result_candidates(const tsg_result* r, uint32_t file, uint32_t rule, const uint64_t** starts, size_t* n);
+/* The (file, rule) pairs of r that have candidates, as 2 * *n uint32 in
+ * ascending order (free with tsg_free): what to ask tsg_result_candidates
+ * for.  Tests only; never used by tsg_scan_batch. */
+int tsg_result_candidate_keys(const tsg_result* r, uint32_t** keys, size_t* n);
+/* K1's other outputs as tsg_prefilter_resident read them back: the '\n' count
+ * of every *chunk_bytes-byte chunk of the packed batch (*n = the number of
+ * chunks; the pointers live as long as r), and one flag word per file.  Tests
+ * only; never used by tsg_scan_batch. */
+int tsg_result_chunk_newlines(const tsg_result* r, const uint16_t** counts, size_t* n, uint32_t* chunk_bytes);
+int tsg_result_file_flags(const tsg_result* r, const uint32_t** flags, size_t* n);
+/* Bit of a file's flag word (engine.h kFileFoldSpecial): the file holds
+ * U+0130, U+212A or U+017F, so the host scans it with the variant tables.  K1
+ * may also set it for a file that shares a 16-byte word of the batch with such
+ * a sequence of a neighbouring file (a superset is safe). */
+#define TSG_FILE_FOLD_SPECIAL 1u
+
+/* CPU model of K1 + K2 alone: prefilter_reference_file on every file -- the
+ * base tables the engine runs (K1c's compressed table when the rule set has
+ * one), no variant pass for fold-special files, no confirmer.  The result
+ * carries the candidates (tsg_result_candidates), one flag word per file
+ * (tsg_result_file_flags: TSG_FILE_FOLD_SPECIAL where the model says
+ * fold-special) and, in its stats, the anchor hits and the distinct
+ * candidates.  The GPU passes must produce exactly these sets
+ * (tests/test_gpu_candidates.py).  Never used by tsg_scan_batch. */
+int tsg_prefilter_table_model(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* offsets, uint32_t nfiles,
+                              tsg_result** out);
 
 /* Host exact confirmer evaluated on every (file, rule) pair with no GPU
  * prefilter (the reference algorithm restated in C++).  For tests of the

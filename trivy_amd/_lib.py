@@ -93,6 +93,14 @@ SIGNATURES = [
     ("tsg_result_stats", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(TsgStats)]),
     ("tsg_result_candidates", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
                                               ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]),
+    ("tsg_result_candidate_keys", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
+                                                  ctypes.POINTER(ctypes.c_size_t)]),
+    ("tsg_result_chunk_newlines", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
+                                                  ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint32)]),
+    ("tsg_result_file_flags", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
+                                              ctypes.POINTER(ctypes.c_size_t)]),
+    ("tsg_prefilter_table_model", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                  ctypes.POINTER(ctypes.c_void_p)]),
     ("tsg_result_free", None, [ctypes.c_void_p]),
     ("tsg_free", None, [ctypes.c_void_p]),
     ("tsg_test_go_sort", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),

@@ -82,6 +82,11 @@ struct tsg_result {
   SecretVec files;
   ScanStats stats;
   std::vector<std::vector<std::vector<uint64_t>>> cands;   // optional [file][rule]
+  // optional (tsg_prefilter_resident, tsg_prefilter_table_model): K1's '\n'
+  // count per chunk of nl_chunk bytes, and the per-file flag words
+  std::vector<uint16_t> chunk_nl;
+  uint32_t nl_chunk = 0;
+  std::vector<uint32_t> file_flags;
   std::vector<std::vector<LayerRef>> layers;               // optional [file][finding] (tsg_result_from_proto)
   // streamed results: the walk outcome, turned into JSON on the first
   // tsg_result_walk_json call (a layer's walked-path list runs to megabytes)
@@ -239,7 +244,11 @@ int tsg_prefilter_resident(tsg_engine* e, const void* d_data, const uint8_t* h_d
   in.nfiles = nfiles;
   auto* r = new tsg_result();
   std::string err;
-  if (!e->eng->prefilter_only(in, &r->cands, &r->stats, &err)) { delete r; return fail(TSG_ERR_HIP, err); }
+  PrefilterRaw raw;
+  if (!e->eng->prefilter_only(in, &r->cands, &r->stats, &err, &raw)) { delete r; return fail(TSG_ERR_HIP, err); }
+  r->chunk_nl = std::move(raw.nl);
+  r->nl_chunk = raw.chunk;
+  r->file_flags = std::move(raw.ff);
   r->files.resize(nfiles);
   *out = r;
   return TSG_OK;
@@ -448,6 +457,41 @@ int tsg_result_candidates(const tsg_result* r, uint32_t f, uint32_t rule, const 
   TSG_API_CATCH
 }
 
+int tsg_result_candidate_keys(const tsg_result* r, uint32_t** keys, size_t* n) {
+  TSG_API_TRY
+  if (!r || !keys || !n) return fail(TSG_ERR_INVALID, "NULL argument");
+  std::vector<uint32_t> k;
+  for (size_t f = 0; f < r->cands.size(); ++f)
+    for (size_t j = 0; j < r->cands[f].size(); ++j)
+      if (!r->cands[f][j].empty()) { k.push_back(static_cast<uint32_t>(f)); k.push_back(static_cast<uint32_t>(j)); }
+  uint32_t* buf = static_cast<uint32_t*>(malloc(std::max<size_t>(k.size(), 1) * sizeof(uint32_t)));
+  if (!buf) return fail(TSG_ERR_INTERNAL, "out of memory");
+  if (!k.empty()) memcpy(buf, k.data(), k.size() * sizeof(uint32_t));
+  *keys = buf;
+  *n = k.size() / 2;
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_result_chunk_newlines(const tsg_result* r, const uint16_t** counts, size_t* n, uint32_t* chunk_bytes) {
+  TSG_API_TRY
+  if (!r || !counts || !n || !chunk_bytes) return fail(TSG_ERR_INVALID, "NULL argument");
+  *counts = r->chunk_nl.data();
+  *n = r->chunk_nl.size();
+  *chunk_bytes = r->nl_chunk;
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_result_file_flags(const tsg_result* r, const uint32_t** flags, size_t* n) {
+  TSG_API_TRY
+  if (!r || !flags || !n) return fail(TSG_ERR_INVALID, "NULL argument");
+  *flags = r->file_flags.data();
+  *n = r->file_flags.size();
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
 // Large results are freed on a reaper thread.  A config-5 result (297k
 // Secrets, 44k findings whose arenas the confirm threads allocated, so most
 // frees cross malloc arenas) took 23 ms to delete: 11% of the next step when
@@ -572,14 +616,36 @@ int tsg_scan_host_reference(const tsg_ruleset* rs, const uint8_t* data, const ui
   TSG_API_CATCH
 }
 
+// The compiled prefilter of the last few rule sets the CPU models ran with
+// (a test calls them once per corpus; compiling a few hundred rules takes
+// seconds).  Keyed by the rule set and by TSG_K1C, which build_prefilter reads.
+static std::shared_ptr<const Prefilter> model_prefilter(const std::shared_ptr<Ruleset>& rs, std::string* err) {
+  struct Entry { std::shared_ptr<Ruleset> rs; std::string env; std::shared_ptr<const Prefilter> pf; };
+  static std::mutex mu;
+  static std::deque<Entry> cache;
+  const char* e = std::getenv("TSG_K1C");
+  const std::string env = e ? e : "";
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    for (const Entry& c : cache) if (c.rs == rs && c.env == env) return c.pf;
+  }
+  auto pf = std::make_shared<Prefilter>();
+  if (!build_prefilter(*rs, pf.get(), err)) return nullptr;
+  std::lock_guard<std::mutex> lk(mu);
+  cache.push_back({rs, env, pf});
+  if (cache.size() > 4) cache.pop_front();
+  return pf;
+}
+
 int tsg_scan_table_model(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* offsets, uint32_t nfiles,
                          const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
                          tsg_result** out) {
   TSG_API_TRY
   if (!rs || !out || !offsets || (nfiles && (!paths || !data))) return fail(TSG_ERR_INVALID, "NULL argument");
-  Prefilter pf;
   std::string err;
-  if (!build_prefilter(*rs->rs, &pf, &err)) return fail(TSG_ERR_INTERNAL, err);
+  const std::shared_ptr<const Prefilter> pfp = model_prefilter(rs->rs, &err);
+  if (!pfp) return fail(TSG_ERR_INTERNAL, err);
+  const Prefilter& pf = *pfp;
   auto* r = new tsg_result();
   r->rs = rs->rs;
   r->files.resize(nfiles);
@@ -630,6 +696,42 @@ int tsg_scan_table_model(const tsg_ruleset* rs, const uint8_t* data, const uint6
                  g_scan_prof[2].load() / 1e6, g_scan_prof[3].load() / 1e6, g_scan_prof[4].load() / 1e6);
   }
   *out = r;
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_prefilter_table_model(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* offsets, uint32_t nfiles,
+                              tsg_result** out) {
+  TSG_API_TRY
+  if (!rs || !out || !offsets || (nfiles && !data)) return fail(TSG_ERR_INVALID, "NULL argument");
+  std::string err;
+  const std::shared_ptr<const Prefilter> pfp = model_prefilter(rs->rs, &err);
+  if (!pfp) return fail(TSG_ERR_INTERNAL, err);
+  const Prefilter& pf = *pfp;
+  std::unique_ptr<tsg_result> r(new tsg_result());
+  r->files.resize(nfiles);
+  r->cands.resize(nfiles);
+  r->file_flags.assign(nfiles, 0);
+  std::atomic<uint32_t> next{0};
+  std::atomic<uint64_t> hits{0}, ncand{0};
+  auto worker = [&]() {
+    std::vector<uint8_t> gate;
+    for (;;) {
+      const uint32_t f = next.fetch_add(1);
+      if (f >= nfiles) break;
+      uint64_t h = 0;
+      if (prefilter_reference_file(pf, data + offsets[f], offsets[f + 1] - offsets[f], &r->cands[f], &gate, &h))
+        r->file_flags[f] = kFileFoldSpecial;
+      hits += h;
+      for (const auto& v : r->cands[f]) ncand += v.size();
+    }
+  };
+  run_threads(static_cast<int>(std::max(1u, std::min(16u, std::thread::hardware_concurrency()))), worker);
+  r->stats.files = nfiles;
+  r->stats.bytes = nfiles ? offsets[nfiles] : 0;
+  r->stats.hits = hits.load();
+  r->stats.candidates = ncand.load();       // distinct (file, rule, start); the engine counts K2's emits
+  *out = r.release();
   return TSG_OK;
   TSG_API_CATCH
 }

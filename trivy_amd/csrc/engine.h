@@ -39,6 +39,18 @@ struct ScanStats {
 // binary[i]}) -- Engine::scan, or (tests only) the CPU model of its passes.
 using BatchScanFn = std::function<bool(const BatchInput& in, SecretVec* results, std::string* err)>;
 
+// K1's per-chunk and per-file outputs of one prefilter_only call (tests).
+struct PrefilterRaw {
+  std::vector<uint16_t> nl;             // '\n' count per K1 chunk of the packed batch
+  std::vector<uint32_t> ff;             // per-file flag word (kFileFoldSpecial)
+  uint32_t chunk = 0;                   // K1 chunk bytes (nl[] granularity)
+};
+// Per-file flag word K1 writes (fflags): bit 0 = the file holds U+0130, U+212A
+// or U+017F, whose lower / upper case is ASCII (the host re-scans it exactly);
+// also set for a file that shares a 16-byte word of the batch with such a
+// sequence of a neighbouring file (k1_special: a superset is safe).
+constexpr uint32_t kFileFoldSpecial = 1u;
+
 struct DeviceTables;
 struct Lane;
 struct GpuOut;
@@ -66,9 +78,11 @@ class Engine {
   bool scan(const BatchInput& in, SecretVec* results, ScanStats* stats, std::string* err);
 
   // Only the two GPU passes (no host confirmation): used by tests to compare
-  // raw candidates.  Resident data on the engine's first device.
+  // raw candidates ([file][rule], exclude-block pseudo-rules after the rules,
+  // as in Prefilter::rules).  Resident data on the engine's first device.
+  // raw (optional): K1's other outputs as they came back from the device.
   bool prefilter_only(const BatchInput& in, std::vector<std::vector<std::vector<uint64_t>>>* cands,
-                      ScanStats* stats, std::string* err);
+                      ScanStats* stats, std::string* err, PrefilterRaw* raw = nullptr);
 
   // Host-feed ceiling (no kernels): streams `bytes` of host memory through
   // the first device's upload ring in pieces of the policy's segment bytes,

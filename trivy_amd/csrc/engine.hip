@@ -593,14 +593,11 @@ __global__ __launch_bounds__(256) void tsg_k2_verify(
         cands[idx].start = start;
       }
     };
-    if (mode == 3) {
-      // presence anchor of a rule evaluated in full on the host: the hit is
-      // the candidate (any one per file suffices)
-      emit(q - fstart_u);
-      continue;
-    }
     if (!(an.flags & 0x200u) && (an.flags & 0x100u)) {
-      // keyword gate: any of the rule's keywords in the file (K1's bits)
+      // keyword gate: any of the rule's keywords in the file (K1's bits).
+      // Before the presence candidates too (as two_pass): without a keyword
+      // the rule cannot match, and a presence candidate makes the host
+      // evaluate it on the whole file.
       const uint32_t* kb = kwbits + static_cast<size_t>(f) * kw_words;
       uint32_t g = an.kw_count ? (kb[an.kw0 >> 5] >> (an.kw0 & 31)) & 1u : 0u;
       for (uint32_t k = 1; k < an.kw_count && !g; ++k) {
@@ -608,6 +605,12 @@ __global__ __launch_bounds__(256) void tsg_k2_verify(
         g = (kb[id >> 5] >> (id & 31)) & 1u;
       }
       if (!g) continue;
+    }
+    if (mode == 3) {
+      // presence anchor of a rule evaluated in full on the host: the hit is
+      // the candidate (any one per file suffices)
+      emit(q - fstart_u);
+      continue;
     }
     if (kStats) atomicAdd(&k2s[kK2Stat * an.rule + 1], 1ull);
     const long long fstart = static_cast<long long>(fstart_u);
@@ -2161,8 +2164,10 @@ bool Engine::seg_geometry(SegRun& r, GpuOut* out, std::string* err) {
   if ((reinterpret_cast<uintptr_t>(r.d_data) & 15) != 0) { *err = "device data must be 16-byte aligned"; return false; }
   // top8 for uploaded segments only: HBM-resident pieces, whose K1 runs beside
   // the previous piece's K2 (K1Chain), ran slower with it (config 2 resident
-  // 5.55 vs 6.06-6.65 ms per step, K1 3.72 vs 3.80 ms, profiles/r8l_*)
-  const int top8_req = r.in.d_data ? 0 : k1_top8_;
+  // 5.55 vs 6.06-6.65 ms per step, K1 3.72 vs 3.80 ms, profiles/r8l_*);
+  // TSG_K1_TOP8=2 (tests) forces the level onto resident batches too, so the
+  // candidate tests reach it through tsg_prefilter_resident
+  const int top8_req = r.in.d_data && k1_top8_ != 2 ? 0 : k1_top8_;
   r.chunk = chunk_ ? chunk_ : k1_chunk_for(r.total, static_cast<uint32_t>(std::max(r.dt.sms, 1)) * 1024u, top8_req,
                                            r.in.d_data != nullptr);
   if (r.chunk > k1_max_chunk(kItemChunks) || r.chunk % 128 != 0) { *err = "K1 chunk exceeds the hit record's offset range"; return false; }
@@ -2565,7 +2570,7 @@ bool Engine::run_segment(DeviceTables& dt, Lane& ln, const Segment& sg, const vo
 }
 
 bool Engine::prefilter_only(const BatchInput& in, std::vector<std::vector<std::vector<uint64_t>>>* cands,
-                            ScanStats* st, std::string* err) {
+                            ScanStats* st, std::string* err, PrefilterRaw* raw) {
   ScanStats local;
   if (!st) st = &local;
   if (!in.d_data) { *err = "prefilter_only needs device-resident data"; return false; }
@@ -2578,13 +2583,20 @@ bool Engine::prefilter_only(const BatchInput& in, std::vector<std::vector<std::v
   const bool ok = run_segment(dt, *ln, sg, in.d_data, nullptr, st, &out, err);
   release_lane(dt, ln);
   if (!ok) return false;
-  const size_t nr = rs_->rules.size();   // real rules only (exclude pseudo-rules follow)
+  const size_t nr = pf_.rules.size();   // the rules, then the exclude-block pseudo-rules
   if (cands) {
     cands->assign(in.nfiles, std::vector<std::vector<uint64_t>>(nr));
-    for (const CandDev& c : out.cands)
-      if (c.rule < nr) (*cands)[c.file][c.rule].push_back(c.start);
+    for (const CandDev& c : out.cands) {
+      if (c.file >= in.nfiles || c.rule >= nr) { *err = "prefilter_only: candidate outside the batch"; return false; }
+      (*cands)[c.file][c.rule].push_back(c.start);
+    }
     for (auto& f : *cands)
       for (auto& v : f) { std::sort(v.begin(), v.end()); v.erase(std::unique(v.begin(), v.end()), v.end()); }
+  }
+  if (raw) {
+    raw->nl = std::move(out.nl);
+    raw->ff = std::move(out.ff);
+    raw->chunk = out.chunk;
   }
   return true;
 }

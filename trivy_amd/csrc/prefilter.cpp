@@ -848,7 +848,7 @@ bool make_scan_dfa(const Nfa& nfa, int s0, uint32_t maxb, ScanDfa* out, std::str
 // each group's DFA over the whole batch; outputs are unioned).
 void two_pass(const Prefilter& pf, const ScanDfa* dfas, size_t ndfa, const std::vector<AnchorInfo>& anchors,
               const uint8_t* data, size_t len, std::vector<std::vector<uint64_t>>* cand, std::vector<uint8_t>* gate,
-              const CompressedScan* comp = nullptr) {
+              const CompressedScan* comp = nullptr, uint64_t* nhits = nullptr) {
   std::vector<uint8_t> kwbit(pf.nkw, 0);
   struct Hit { uint64_t end; uint32_t anchor; };
   std::vector<Hit> hits;
@@ -885,6 +885,7 @@ void two_pass(const Prefilter& pf, const ScanDfa* dfas, size_t ndfa, const std::
       }
     }
   }
+  if (nhits) *nhits = hits.size();
   gate->assign(pf.rules.size(), 0);
   for (size_t r = 0; r < pf.rules.size(); ++r) {
     const RuleGpuInfo& gi = pf.rules[r];
@@ -1495,11 +1496,20 @@ bool build_prefilter(const Ruleset& rs, Prefilter* pf, std::string* err) {
                 (ix.usable ? std::to_string(ix.out.size()) + " AC states, " +
                                  std::to_string(__builtin_popcountll(ix.always)) + " ungated regexes"
                            : std::string("unused (plain loop)")) + "\n";
+  // RuleGpuInfo::mode of every rule, then of the exclude-block pseudo-rules,
+  // and how each keyword gate is evaluated: g = on the GPU (K1's bits),
+  // a = always open, h = on the host (K2 lets every hit through)
+  std::string modes = "rule modes:", gates = "rule gates:";
+  for (const RuleGpuInfo& gi : pf->rules) {
+    modes += " " + std::to_string(gi.mode);
+    gates += gi.always_gate ? " a" : gi.gate_on_gpu ? " g" : " h";
+  }
+  pf->report += modes + "\n" + gates + "\n";
   return true;
 }
 
 bool prefilter_reference_file(const Prefilter& pf, const uint8_t* data, size_t len,
-                              std::vector<std::vector<uint64_t>>* cand, std::vector<uint8_t>* gate) {
+                              std::vector<std::vector<uint64_t>>* cand, std::vector<uint8_t>* gate, uint64_t* nhits) {
   bool special = false;
   for (size_t p = 1; p < len; ++p) {
     if (fold_special_at(p >= 2 ? data[p - 2] : 0, data[p - 1], data[p])) { special = true; break; }
@@ -1507,7 +1517,7 @@ bool prefilter_reference_file(const Prefilter& pf, const uint8_t* data, size_t l
   // the tables the engine runs: K1c's compressed one-pass table when the
   // rule set has one, else the scan-DFA groups
   two_pass(pf, pf.groups.data(), pf.groups.size(), pf.anchors, data, len, cand, gate,
-           pf.compressed.ok ? &pf.compressed : nullptr);
+           pf.compressed.ok ? &pf.compressed : nullptr, nhits);
   return special;
 }
 

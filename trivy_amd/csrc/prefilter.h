@@ -164,10 +164,11 @@ bool literal_gate(const re::Node& ast, re::LitGate* out, bool* bounded, uint32_t
 // candidate starts and keyword-gate bits for one file.
 // Returns true when the file contains U+0130 (C4 B0), U+212A (E2 84 AA) or
 // U+017F (C5 BF): the scan DFA is ASCII-only, so such files are evaluated
-// exactly on the host (FilePlan == nullptr).
+// exactly on the host (FilePlan == nullptr).  nhits (optional): the anchor
+// hits of the scan pass, K1's hit records for this file.
 bool prefilter_reference_file(const Prefilter& pf, const uint8_t* data, size_t len,
                               std::vector<std::vector<uint64_t>>* cand_per_rule,
-                              std::vector<uint8_t>* gate_per_rule);
+                              std::vector<uint8_t>* gate_per_rule, uint64_t* nhits = nullptr);
 
 // Host path for fold-special files: the same two passes with the variant scan
 // DFA (exact for those runes).  Product code (used by Engine::scan).

@@ -587,6 +587,106 @@ def scan_table_model(scanner, args_list):
     return out
 
 
+def _result_candidates(res):
+    """{(file, rule): sorted np.uint64 starts} of a result's non-empty
+    candidate lists (tsg_result_candidate_keys + tsg_result_candidates)."""
+    L = _lib.lib()
+    kp, kn = ctypes.c_void_p(), ctypes.c_size_t()
+    _lib.check(L.tsg_result_candidate_keys(res, ctypes.byref(kp), ctypes.byref(kn)))
+    try:
+        keys = np.ctypeslib.as_array(ctypes.cast(kp, ctypes.POINTER(ctypes.c_uint32)),
+                                     shape=(kn.value, 2)).copy() if kn.value else np.zeros((0, 2), np.uint32)
+    finally:
+        L.tsg_free(kp)
+    out = {}
+    p, n = ctypes.c_void_p(), ctypes.c_size_t()
+    for f, r in keys.tolist():
+        _lib.check(L.tsg_result_candidates(res, f, r, ctypes.byref(p), ctypes.byref(n)))
+        out[(f, r)] = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint64)), shape=(n.value,)).copy()
+    return out
+
+
+def _result_file_flags(res):
+    L = _lib.lib()
+    p, n = ctypes.c_void_p(), ctypes.c_size_t()
+    _lib.check(L.tsg_result_file_flags(res, ctypes.byref(p), ctypes.byref(n)))
+    if not n.value:
+        return np.zeros(0, np.uint32)
+    return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint32)), shape=(n.value,)).copy()
+
+
+FILE_FOLD_SPECIAL = 1      # TSG_FILE_FOLD_SPECIAL (trivy_secret_test.h)
+FULL_SCAN_START = np.uint64(0xFFFFFFFFFFFFFFFF)    # kFullScanStart (prefilter.h)
+
+
+def prefilter_table_model(scanner, args_list, with_info=False):
+    """CPU model of K1 + K2 alone on the packed batch (tsg_prefilter_table_model):
+    {(file, rule): np.uint64 starts}; with_info adds {"special": one bool per
+    file, "hits": anchor hits, "candidates": distinct candidates}.  Tests only."""
+    data, offsets = pack(args_list)
+    res = ctypes.c_void_p()
+    _lib.check(_lib.lib().tsg_prefilter_table_model(scanner._rs, data.ctypes.data, offsets.ctypes.data,
+                                                    len(args_list), ctypes.byref(res)))
+    try:
+        cands = _result_candidates(res)
+        st = _lib.result_stats(res)
+        special = (_result_file_flags(res) & FILE_FOLD_SPECIAL) != 0
+    finally:
+        _lib.lib().tsg_result_free(res)
+    if not with_info:
+        return cands
+    return cands, {"special": special, "hits": st["hits"], "candidates": st["candidates"]}
+
+
+def table_model_candidates(scanner, args_list):
+    """The candidates tsg_scan_table_model planned its confirmation from: the
+    base tables' for a file without fold-special runes, the variant tables'
+    for one with them.  Tests only."""
+    data, offsets = pack(args_list)
+    paths, lens, _keep = _lib.pack_paths([a.FilePath for a in args_list])
+    binary = np.array([1 if a.Binary else 0 for a in args_list] or [0], dtype=np.uint8)
+    res = ctypes.c_void_p()
+    _lib.check(_lib.lib().tsg_scan_table_model(scanner._rs, data.ctypes.data, offsets.ctypes.data,
+                                               len(args_list), paths, lens, binary.ctypes.data,
+                                               ctypes.byref(res)))
+    try:
+        return _result_candidates(res)
+    finally:
+        _lib.lib().tsg_result_free(res)
+
+
+def prefilter_resident(scanner, args_list, pad=None, device="cuda:0"):
+    """K1 + K2 on the GPU over the packed batch, uploaded with torch
+    (tsg_prefilter_resident): ({(file, rule): np.uint64 starts}, info) with
+    info = {"chunk_newlines": np.uint16 per K1 chunk, "chunk_bytes", "flags":
+    np.uint32 per file, "stats"}.  pad: up to 64 bytes that follow the batch in
+    device memory in place of zeros (the kernels may read them, never use
+    them).  Tests only."""
+    import torch
+    L = _lib.lib()
+    data, offsets = pack(args_list)
+    if pad:
+        total = int(offsets[-1])
+        data[total:total + len(pad[:64])] = np.frombuffer(pad[:64], dtype=np.uint8)
+    d = torch.from_numpy(data).to(device)
+    torch.cuda.synchronize()
+    res = ctypes.c_void_p()
+    _lib.check(L.tsg_prefilter_resident(scanner.engine(), ctypes.c_void_p(d.data_ptr()), data.ctypes.data,
+                                        offsets.ctypes.data, len(args_list), ctypes.byref(res)))
+    try:
+        cands = _result_candidates(res)
+        p, n, ch = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_uint32()
+        _lib.check(L.tsg_result_chunk_newlines(res, ctypes.byref(p), ctypes.byref(n), ctypes.byref(ch)))
+        nl = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint16)), shape=(n.value,)).copy() \
+            if n.value else np.zeros(0, np.uint16)
+        info = {"chunk_newlines": nl, "chunk_bytes": ch.value, "flags": _result_file_flags(res),
+                "stats": _lib.result_stats(res)}
+    finally:
+        L.tsg_result_free(res)
+    del d
+    return cands, info
+
+
 def prefilter_report(scanner):
     buf = ctypes.c_void_p()
     _lib.check(_lib.lib().tsg_prefilter_report(scanner._rs, ctypes.byref(buf)))
