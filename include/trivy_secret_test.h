@@ -39,6 +39,42 @@ int tsg_result_candidate_keys(const tsg_result* r, uint32_t** keys, size_t* n);
  * only; never used by tsg_scan_batch. */
 int tsg_result_chunk_newlines(const tsg_result* r, const uint16_t** counts, size_t* n, uint32_t* chunk_bytes);
 int tsg_result_file_flags(const tsg_result* r, const uint32_t** flags, size_t* n);
+/* Test hook: while `on`, the results of tsg_scan_batch and
+ * tsg_scan_batch_resident on this engine carry, next to the findings, the raw
+ * outputs of the GPU passes as Engine::scan saw them, segment by segment:
+ *  - every real file's candidates, in batch file indices and file-relative
+ *    starts, sorted and de-duplicated per (file, rule)
+ *    (tsg_result_candidates, tsg_result_candidate_keys), and its flag word
+ *    (tsg_result_file_flags, one per file of the batch);
+ *  - one record per segment, in segment order (tsg_result_raw_segments,
+ *    tsg_result_raw_segment): where the batch was cut, the segment's K1 chunk
+ *    size, its '\n' count per chunk (the chunk grid starts at the lead, b0 -
+ *    lead_bytes, when the segment has one), its K1 anchor hits (the lead's
+ *    included), and what the passes said about the lead -- the pseudo-file of
+ *    the bytes between the 256-byte boundary below a resident piece's first
+ *    file and that file, whose results the product drops: its flag word, the
+ *    number of candidates K2 emitted for it and their distinct (rule, start)
+ *    pairs in ascending order.
+ * The pointers of a record live as long as r.  Off (the default), a scan takes
+ * one more branch per segment and copies nothing.  No product entry point
+ * calls it. */
+typedef struct {
+  uint32_t f0, nfiles, lead;       /* first file of the batch; the segment's own files; 1 = it ran with a lead */
+  uint32_t chunk_bytes;            /* K1 chunk bytes of this segment */
+  uint64_t b0, bytes, lead_bytes;  /* first byte of f0 in the batch; bytes of the own files; bytes of the lead */
+  uint64_t hits;                   /* K1 anchor hits, the lead's included */
+  uint32_t lead_flags;             /* the lead's flag word */
+  uint32_t lead_emitted;           /* candidates K2 emitted for the lead, duplicates included */
+  const uint16_t* chunk_newlines;  /* nchunks counts */
+  size_t nchunks;
+  const uint32_t* lead_cand_rules; /* nlead_cands distinct (rule, start) pairs of the lead */
+  const uint64_t* lead_cand_starts;
+  size_t nlead_cands;
+} tsg_raw_segment;
+int tsg_test_keep_raw(tsg_engine* e, int on);
+int tsg_result_raw_segments(const tsg_result* r, size_t* n);
+int tsg_result_raw_segment(const tsg_result* r, size_t k, tsg_raw_segment* rec);
+
 /* Bit of a file's flag word (engine.h kFileFoldSpecial): the file holds
  * U+0130, U+212A or U+017F, so the host scans it with the variant tables.  K1
  * may also set it for a file that shares a 16-byte word of the batch with such

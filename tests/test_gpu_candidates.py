@@ -13,16 +13,16 @@ setting,
   the chunk size the stats report, one entry per chunk;
 * K1's per-file fold-special flag equals the model's -- but for the files of
   one corpus that share a 16-byte word with a neighbour's sequence, where K1
-  flags a superset by design (see _check).
+  flags a superset by design (see _candidate_check.check).
 
 The conditions that make these comparisons meaningful (every probe fires,
 cut probes are silent, the overflow inputs overflow, ...) are asserted on the
 CPU in tests/test_candidate_corpus.py.
 """
-import numpy as np
 import pytest
 
 import _edge_corpus as EC
+from _candidate_check import check as _check          # (shared with tests/test_gpu_paths.py)
 from trivy_amd import secret as S
 
 pytestmark = pytest.mark.gpu
@@ -77,72 +77,6 @@ def _gpu_scanner(name, setting, monkeypatch):
     sc = S.Scanner(EC.ruleset_config(name)[0])
     sc.engine()
     return sc
-
-
-def _where(c, f, start, chunk):
-    """Names the edges next to a candidate start, for a failure message."""
-    if start == int(S.FULL_SCAN_START):
-        return "start kFullScanStart"
-    b = int(c.offsets[f]) + start
-    return ("start %d = batch offset %d (mod chunk %d: %d, mod 64: %d, mod 4 chunks: %d, mod 8 chunks: %d, "
-            "mod 64 KiB: %d; %d bytes before the file's end; batch of %d bytes)"
-            % (start, b, chunk, b % chunk, b % 64, b % (4 * chunk), b % (8 * chunk), b % EC.BLOCK,
-               int(c.offsets[f + 1]) - b, c.nbytes))
-
-
-def _check(c, rule_ids, got, info, want, winfo, expect_chunk=None):
-    chunk = info["chunk_bytes"]
-    # ---- candidates: the same keys, the same sorted starts
-    for key in sorted(set(got) | set(want)):
-        g = got.get(key, np.zeros(0, np.uint64))
-        w = want.get(key, np.zeros(0, np.uint64))
-        if np.array_equal(g, w):
-            continue
-        f, r = key
-        missing, extra = np.setdiff1d(w, g), np.setdiff1d(g, w)
-        kind, start = ("the GPU lacks", int(missing[0])) if len(missing) else ("the GPU adds", int(extra[0]))
-        rid = rule_ids[r] if r < len(rule_ids) else "exclude-block #%d" % (r - len(rule_ids))
-        pytest.fail("%s: %s a candidate (%d missing, %d extra in this list): file %d %s (%d bytes), rule %d %s, %s"
-                    % (c.name, kind, len(missing), len(extra), f, c.args[f].FilePath, len(c.args[f].Content), r, rid,
-                       _where(c, f, start, chunk)))
-    assert info["stats"]["hits"] == winfo["hits"], (c.name, "anchor hits", info["stats"]["hits"], winfo["hits"])
-    # ---- newline counts: one per chunk of the packed batch
-    assert chunk == info["stats"]["chunk_bytes"] and chunk > 0
-    if expect_chunk:
-        assert chunk == expect_chunk
-    data, offsets = S.pack(c.args)
-    total = int(offsets[-1])
-    nl = info["chunk_newlines"]
-    assert len(nl) == -(-total // chunk), (c.name, len(nl), total, chunk)
-    ref = np.add.reduceat((data[:total] == 10).astype(np.int64), np.arange(0, total, chunk)) if total else np.zeros(0)
-    bad = np.nonzero(nl.astype(np.int64) != ref)[0]
-    assert len(bad) == 0, ("%s: newline count of chunk %d (batch offset %d, chunk %d): GPU %d, batch %d; %d chunks differ"
-                           % (c.name, bad[0], bad[0] * chunk, chunk, nl[bad[0]], ref[bad[0]], len(bad)))
-    # ---- file flags: bit 0 (engine.h kFileFoldSpecial) is the only bit K1 sets
-    flags = info["flags"]
-    assert len(flags) == len(c.args)
-    assert not (flags & ~np.uint32(S.FILE_FOLD_SPECIAL)).any()
-    gs = (flags & S.FILE_FOLD_SPECIAL) != 0
-    bad = gs != winfo["special"]
-    if c.note.get("flags") == "word16":
-        # The one exception, by K1's design (engine.hip k1_special): a 16-byte
-        # word that holds a file boundary is checked as one piece and every
-        # file overlapping it is flagged -- a superset, safe because a flagged
-        # file is only scanned more carefully.  So a file the model does not
-        # call special may be flagged iff it shares a 16-byte word of the
-        # batch with the end of a sequence; a special file is always flagged.
-        words = EC.fold_special_words(data, total)
-        for f in np.nonzero(bad)[0]:
-            lo, hi = int(offsets[f]), int(offsets[f + 1])
-            near = hi > lo and ((words * 16 < hi) & (words * 16 + 16 > lo)).any()
-            if gs[f] and not winfo["special"][f] and near:
-                bad[f] = False
-    bad = np.nonzero(bad)[0]
-    if len(bad):
-        f = int(bad[0])
-        pytest.fail("%s: fold-special flag of file %d %s (%d bytes at batch offset %d, mod 16: %d): GPU %d, model %d; "
-                    "%d files differ" % (c.name, f, c.args[f].FilePath, len(c.args[f].Content), int(c.offsets[f]),
-                                          int(c.offsets[f]) % 16, gs[f], winfo["special"][f], len(bad)))
 
 
 def _run(name, setting, group, monkeypatch):

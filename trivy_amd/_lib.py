@@ -35,6 +35,15 @@ class TsgSegmentInfo(ctypes.Structure):
                 ("b0", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("d_data", ctypes.c_uint64)]
 
 
+class TsgRawSegment(ctypes.Structure):
+    _fields_ = [("f0", ctypes.c_uint32), ("nfiles", ctypes.c_uint32), ("lead", ctypes.c_uint32),
+                ("chunk_bytes", ctypes.c_uint32), ("b0", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
+                ("lead_bytes", ctypes.c_uint64), ("hits", ctypes.c_uint64), ("lead_flags", ctypes.c_uint32),
+                ("lead_emitted", ctypes.c_uint32), ("chunk_newlines", ctypes.c_void_p), ("nchunks", ctypes.c_size_t),
+                ("lead_cand_rules", ctypes.c_void_p), ("lead_cand_starts", ctypes.c_void_p),
+                ("nlead_cands", ctypes.c_size_t)]
+
+
 class TsgStats(ctypes.Structure):
     _fields_ = [("k1_ms", ctypes.c_double), ("k2_ms", ctypes.c_double), ("h2d_ms", ctypes.c_double),
                 ("d2h_ms", ctypes.c_double), ("host_ms", ctypes.c_double), ("total_ms", ctypes.c_double),
@@ -115,6 +124,9 @@ SIGNATURES = [
                                                ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p, ctypes.c_size_t]),
     ("tsg_test_engine_footprint", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
                                                   ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
+    ("tsg_test_keep_raw", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    ("tsg_result_raw_segments", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tsg_result_raw_segment", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(TsgRawSegment)]),
     ("tsg_test_inject_segment_failures", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
     ("tsg_test_wire_pack", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p,
                                            ctypes.c_size_t, ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t),

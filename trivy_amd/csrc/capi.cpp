@@ -87,6 +87,7 @@ struct tsg_result {
   std::vector<uint16_t> chunk_nl;
   uint32_t nl_chunk = 0;
   std::vector<uint32_t> file_flags;
+  std::vector<RawSegment> raw_segs;                         // optional (tsg_test_keep_raw): one per segment of the scan
   std::vector<std::vector<LayerRef>> layers;               // optional [file][finding] (tsg_result_from_proto)
   // streamed results: the walk outcome, turned into JSON on the first
   // tsg_result_walk_json call (a layer's walked-path list runs to megabytes)
@@ -212,7 +213,16 @@ static int do_scan(tsg_engine* e, const void* d_data, const uint8_t* h_data, con
   auto* r = new tsg_result();
   r->rs = e->eng->ruleset();
   std::string err;
-  if (!e->eng->scan(in, &r->files, &r->stats, &err)) { delete r; return fail(TSG_ERR_HIP, err); }
+  if (!e->eng->keep_raw()) {
+    if (!e->eng->scan(in, &r->files, &r->stats, &err)) { delete r; return fail(TSG_ERR_HIP, err); }
+  } else {
+    // test hook (tsg_test_keep_raw): the segments' GPU outputs beside the findings
+    RawScan raw;
+    if (!e->eng->scan(in, &r->files, &r->stats, &err, &raw)) { delete r; return fail(TSG_ERR_HIP, err); }
+    r->cands = std::move(raw.cands);
+    r->file_flags = std::move(raw.ff);
+    r->raw_segs = std::move(raw.segs);
+  }
   *out = r;
   return TSG_OK;
 }
@@ -878,6 +888,37 @@ int tsg_test_engine_footprint(tsg_engine* e, uint32_t* lanes, uint32_t* calls, u
   TSG_API_TRY
   if (!e || !lanes || !calls || !pool_threads) return fail(TSG_ERR_INVALID, "NULL argument");
   e->eng->footprint(lanes, calls, pool_threads);
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_test_keep_raw(tsg_engine* e, int on) {
+  TSG_API_TRY
+  if (!e) return fail(TSG_ERR_INVALID, "engine is NULL");
+  e->eng->set_keep_raw(on != 0);
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_result_raw_segments(const tsg_result* r, size_t* n) {
+  TSG_API_TRY
+  if (!r || !n) return fail(TSG_ERR_INVALID, "NULL argument");
+  *n = r->raw_segs.size();
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_result_raw_segment(const tsg_result* r, size_t k, tsg_raw_segment* rec) {
+  TSG_API_TRY
+  if (!r || !rec) return fail(TSG_ERR_INVALID, "NULL argument");
+  if (k >= r->raw_segs.size()) return fail(TSG_ERR_INVALID, "no such segment");
+  const RawSegment& s = r->raw_segs[k];
+  rec->f0 = s.f0; rec->nfiles = s.nfiles; rec->lead = s.lead; rec->chunk_bytes = s.chunk;
+  rec->b0 = s.b0; rec->bytes = s.bytes; rec->lead_bytes = s.lead_bytes; rec->hits = s.hits;
+  rec->lead_flags = s.lead_flags; rec->lead_emitted = s.lead_emitted;
+  rec->chunk_newlines = s.nl.data(); rec->nchunks = s.nl.size();
+  rec->lead_cand_rules = s.lead_rules.data(); rec->lead_cand_starts = s.lead_starts.data();
+  rec->nlead_cands = s.lead_rules.size();
   return TSG_OK;
   TSG_API_CATCH
 }

@@ -51,6 +51,27 @@ struct PrefilterRaw {
 // sequence of a neighbouring file (k1_special: a superset is safe).
 constexpr uint32_t kFileFoldSpecial = 1u;
 
+// Test hook (tsg_test_keep_raw): what the GPU passes of one scan() gave, kept
+// beside the findings -- one record per segment as Engine::scan cut the batch,
+// and every real file's candidates and flag word in batch file indices.
+struct RawSegment {
+  uint32_t f0 = 0, nfiles = 0, lead = 0;  // first file of the batch, the segment's own files, 1 = it ran with a lead file
+  uint64_t b0 = 0, bytes = 0, lead_bytes = 0;
+  uint32_t chunk = 0;                   // K1 chunk bytes of this segment
+  uint64_t hits = 0;                    // K1 anchor hits (the lead's included)
+  std::vector<uint16_t> nl;             // '\n' per chunk; the grid starts at b0 - lead_bytes
+  uint32_t lead_flags = 0;              // the lead's flag word
+  uint32_t lead_emitted = 0;            // candidates K2 emitted for the lead (duplicates included)
+  std::vector<uint32_t> lead_rules;     // the lead's distinct candidates, sorted by (rule, start)
+  std::vector<uint64_t> lead_starts;
+};
+struct RawScan {
+  std::vector<RawSegment> segs;
+  std::vector<std::vector<std::vector<uint64_t>>> cands;   // [file][rule]; a file without candidates has no rule lists
+  std::vector<uint32_t> ff;
+  std::string error;                    // a candidate outside its segment's files or the rule table
+};
+
 struct DeviceTables;
 struct Lane;
 struct GpuOut;
@@ -75,7 +96,8 @@ class Engine {
   ~Engine();
 
   // results[i] is Scanner.Scan(ScanArgs{paths[i], data[off[i]:off[i+1]], binary[i]}).
-  bool scan(const BatchInput& in, SecretVec* results, ScanStats* stats, std::string* err);
+  // raw (tests only, tsg_test_keep_raw): receives the segments' GPU outputs.
+  bool scan(const BatchInput& in, SecretVec* results, ScanStats* stats, std::string* err, RawScan* raw = nullptr);
 
   // Only the two GPU passes (no host confirmation): used by tests to compare
   // raw candidates ([file][rule], exclude-block pseudo-rules after the rules,
@@ -100,6 +122,9 @@ class Engine {
   void footprint(uint32_t* lanes, uint32_t* calls, uint32_t* pool_threads);
   // Test hook: the next n run_segment calls fail before their first launch.
   void inject_segment_failures(uint32_t n) { inject_fail_.store(n); }
+  // Test hook (tsg_test_keep_raw): the C-ABI's scans pass a RawScan while it is on.
+  void set_keep_raw(bool on) { keep_raw_.store(on); }
+  bool keep_raw() const { return keep_raw_.load(std::memory_order_relaxed); }
 
   const Prefilter& prefilter() const { return pf_; }
   std::shared_ptr<const Ruleset> ruleset() const { return rs_; }
@@ -203,6 +228,7 @@ class Engine {
   int k2_abl_ = 0;                      // TSG_K2_ABL (probe library): K2 trace / no-walk measurement builds
   bool host_profile_ = false;           // TSG_HOST_PROFILE=1: per-segment host confirm breakdown on stderr
   std::atomic<uint32_t> inject_fail_{0};
+  std::atomic<bool> keep_raw_{false};
   std::mutex k2s_mu_;
   std::vector<unsigned long long> k2s_;  // 4 per rule: hits, past the keyword gate, verify starts, bytes walked
   SegmentPolicy seg_;                   // where a batch is cut (segments.h: TSG_PIECES, TSG_SEGMENT_BYTES, ...)

@@ -1953,8 +1953,9 @@ std::unique_ptr<Engine> Engine::create(std::shared_ptr<const Ruleset> rs, const 
   env_double("TSG_FIRST_PIECE_FEW", 0.0, false, 1.0, &sp.first_piece_few);
   env_double("TSG_LAST_PIECE", 0.0, true, 0.5, &sp.last_piece);
   env_int("TSG_MIN_PIECE_BYTES", 1, INT64_MAX, &sp.min_piece);
-  env_int("TSG_SEGMENT_BYTES", 4096, INT64_MAX, &sp.segment);
-  env_int("TSG_SEGMENT_MIN", 4096, INT64_MAX, &sp.segment_min);
+  // (from 256 bytes: tests cut batches of a few KB into several segments)
+  env_int("TSG_SEGMENT_BYTES", 256, INT64_MAX, &sp.segment);
+  env_int("TSG_SEGMENT_MIN", 256, INT64_MAX, &sp.segment_min);
   if (const char* c = std::getenv("TSG_SEGMENT_BALANCED")) sp.balanced = std::atoi(c) != 0;
   if (const char* c = std::getenv("TSG_K1_ABL")) e->k1_abl_ = std::atoi(c);   // K1 measurement builds (kAbl bits)
   if (const char* c = std::getenv("TSG_K2_STATS")) e->k2_stats_ = std::atoi(c) != 0;
@@ -3269,7 +3270,44 @@ void Engine::confirm_segment(CallCtx& cc, const Segment& sg, GpuOut& g, Secret* 
 struct ScanJob {
   size_t seg = 0;
   GpuOut out;
+  uint64_t hits = 0;                   // K1 anchor hits of the segment (tsg_test_keep_raw)
 };
+
+namespace {
+
+// Test hook (tsg_test_keep_raw): one segment's GPU outputs into the scan's
+// RawScan, before the confirmation reads them -- the lead's under its record,
+// the real files' under their batch indices.
+void record_raw_segment(const Segment& sg, const ScanJob& job, size_t nrules, RawScan* raw) {
+  const GpuOut& g = job.out;
+  RawSegment& rec = raw->segs[job.seg];
+  rec.f0 = sg.f0;
+  rec.nfiles = sg.in.nfiles - sg.lead;
+  rec.lead = sg.lead;
+  rec.b0 = sg.b0;
+  rec.bytes = sg.bytes;
+  rec.lead_bytes = sg.lead ? sg.in.offsets[1] : 0;
+  rec.chunk = g.chunk;
+  rec.hits = job.hits;
+  rec.nl = g.nl;
+  if (g.ff.size() != sg.in.nfiles) { raw->error = "raw outputs: the flag words do not cover the segment's files"; return; }
+  if (sg.lead) rec.lead_flags = g.ff[0];
+  for (uint32_t f = sg.lead; f < sg.in.nfiles; ++f) raw->ff[sg.f0 + f - sg.lead] = g.ff[f];
+  std::vector<std::pair<uint32_t, uint64_t>> lead;
+  for (const CandDev& c : g.cands) {
+    if (c.file >= sg.in.nfiles || c.rule >= nrules) { raw->error = "raw outputs: candidate outside the segment"; return; }
+    if (c.file < sg.lead) { lead.emplace_back(c.rule, c.start); continue; }
+    auto& per_rule = raw->cands[sg.f0 + c.file - sg.lead];
+    if (per_rule.empty()) per_rule.resize(nrules);
+    per_rule[c.rule].push_back(c.start);
+  }
+  rec.lead_emitted = static_cast<uint32_t>(lead.size());
+  std::sort(lead.begin(), lead.end());
+  lead.erase(std::unique(lead.begin(), lead.end()), lead.end());
+  for (const auto& c : lead) { rec.lead_rules.push_back(c.first); rec.lead_starts.push_back(c.second); }
+}
+
+}  // namespace
 
 // What the device drivers of one scan() share.
 struct ScanCall {
@@ -3410,6 +3448,7 @@ struct SegmentDriver {
       int64_t prev = sc.feed_end_ns.load();
       while (ns > prev && !sc.feed_end_ns.compare_exchange_weak(prev, ns)) {}
     }
+    job->hits = sst.hits;
     add_stats(&dst, sst);
     pending = std::move(job);
     return true;
@@ -3494,7 +3533,7 @@ struct SegmentDriver {
 // Every segment is a self-contained batch (offsets rebased to 0, data a
 // 16-byte aligned sub-range; segments.h), so the kernels are unchanged and the
 // result is the one-segment result.
-bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::string* err) {
+bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::string* err, RawScan* raw) {
   ScanStats local;
   if (!st) st = &local;
   *st = ScanStats();
@@ -3507,6 +3546,11 @@ bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::
   const uint64_t total = in.nfiles ? in.offsets[in.nfiles] : 0;
   st->bytes = total;
   st->files = in.nfiles;
+  if (raw) {
+    *raw = RawScan();
+    raw->cands.resize(in.nfiles);
+    raw->ff.assign(in.nfiles, 0);
+  }
   if (in.nfiles == 0 || total == 0) {
     // nothing for the GPU: every file is empty, so only the global
     // allow-path outcome (scanner.go:381-386) can make a Secret non-empty
@@ -3529,6 +3573,7 @@ bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::
   }
   std::vector<Segment> segs;
   plan_segments(in, resident, seg_, &segs);
+  if (raw) raw->segs.resize(segs.size());
   for (auto& d : dev_) {
     if (resident || drivers.size() >= segs.size()) break;
     drivers.push_back(d.get());
@@ -3574,6 +3619,8 @@ bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::
         const Segment& sg = segs[job.seg];
         const double c_start = host_profile_ ? ms_since(sc.t_feed0) : 0.0;
         sc.confirmer_idle.store(false, std::memory_order_release);
+        // (by job.seg: segments arrive in any order; before the confirmation uses the outputs)
+        if (raw) record_raw_segment(sg, job, pf_.rules.size(), raw);
         // (drivers that block on an event leave every core to the pool)
         confirm_segment(*cc, sg, job.out, results->data() + sg.f0, &nconf, &nfind, left > 0 && !dual);
         sc.confirmer_idle.store(true, std::memory_order_release);
@@ -3583,6 +3630,11 @@ bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::
       pop_spin_us_, &run_err);
   release_call(cc);
   if (!run_ok) { *err = run_err; return false; }
+  if (raw) {
+    if (!raw->error.empty()) { *err = raw->error; return false; }
+    for (auto& f : raw->cands)
+      for (auto& v : f) { std::sort(v.begin(), v.end()); v.erase(std::unique(v.begin(), v.end()), v.end()); }
+  }
   st->bytes = total;
   st->files = in.nfiles;
   st->pieces = static_cast<uint32_t>(segs.size());

@@ -687,6 +687,105 @@ def prefilter_resident(scanner, args_list, pad=None, device="cuda:0"):
     return cands, info
 
 
+def scan_raw(scanner, args_list, resident=False, base=0, pinned=True, data_shift=0, device="cuda:0"):
+    """tsg_scan_batch (or, resident, tsg_scan_batch_resident) with the raw-output
+    hook on (tsg_test_keep_raw; it stays on for the scanner's engine): the real
+    Engine::scan with its cuts, upload ring, wire feed, direct stage, leads and
+    pooled lanes.  Returns (findings, {(file, rule): np.uint64 starts}, info)
+    with info = {"flags": np.uint32 per file, "segments": one dict per segment
+    (f0, nfiles, lead, b0, bytes, lead_bytes, chunk_bytes, hits, lead_flags,
+    lead_emitted, "chunk_newlines": np.uint16 per chunk, "lead_cands":
+    [(rule, start)]), "stats"}.
+
+    Upload: the batch lies data_shift bytes into a tsg_alloc_pinned buffer
+    (pinned) or a numpy array (pageable).  resident: it lies `base` bytes (a
+    multiple of 16) above a 256-byte boundary of device memory, uploaded with
+    torch; the host copy the confirmer needs is the packed array.  Tests only."""
+    L = _lib.lib()
+    data, offsets = pack(args_list)
+    n = len(data)
+    paths, lens, _keep = _lib.pack_paths([a.FilePath for a in args_list])
+    binary = np.array([1 if a.Binary else 0 for a in args_list] or [0], dtype=np.uint8)
+    eng = scanner.engine()
+    _lib.check(L.tsg_test_keep_raw(eng, 1))
+    res = ctypes.c_void_p()
+    pin = ctypes.c_void_p()
+    d = None
+    try:
+        if resident:
+            import torch
+            full = torch.zeros(base + n + 256, dtype=torch.uint8, device=device)
+            if full.data_ptr() % 256 != 0 or base % 16 != 0:
+                raise ValueError("scan_raw: device allocation or base is not aligned")
+            d = full[base:base + n]
+            d.copy_(torch.from_numpy(data))
+            torch.cuda.synchronize()
+            _lib.check(L.tsg_scan_batch_resident(eng, ctypes.c_void_p(d.data_ptr()), data.ctypes.data,
+                                                 offsets.ctypes.data, len(args_list), paths, lens, binary.ctypes.data,
+                                                 ctypes.byref(res)))
+        else:
+            if pinned:
+                _lib.check(L.tsg_alloc_pinned(n + data_shift, ctypes.byref(pin)))
+                host = np.ctypeslib.as_array(ctypes.cast(pin, ctypes.POINTER(ctypes.c_uint8)), shape=(n + data_shift,))
+            else:
+                host = np.zeros(n + data_shift, np.uint8)
+            host[:data_shift] = 0x41
+            host[data_shift:] = data
+            _lib.check(L.tsg_scan_batch(eng, host.ctypes.data + data_shift, offsets.ctypes.data, len(args_list), paths,
+                                        lens, binary.ctypes.data, ctypes.byref(res)))
+        findings = _lib.result_json(res)
+        for s in findings:
+            s.pop("Error", None)
+        ns = ctypes.c_size_t()
+        _lib.check(L.tsg_result_raw_segments(res, ctypes.byref(ns)))
+        segs = []
+        for k in range(ns.value):
+            rec = _lib.TsgRawSegment()
+            _lib.check(L.tsg_result_raw_segment(res, k, ctypes.byref(rec)))
+            sd = {f: getattr(rec, f) for f in ("f0", "nfiles", "lead", "chunk_bytes", "b0", "bytes", "lead_bytes", "hits",
+                                               "lead_flags", "lead_emitted")}
+
+            def arr(p, ctype, dtype, count):
+                if not count:
+                    return np.zeros(0, dtype)
+                return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctype)), shape=(count,)).copy()
+            sd["chunk_newlines"] = arr(rec.chunk_newlines, ctypes.c_uint16, np.uint16, rec.nchunks)
+            sd["lead_cands"] = list(zip(arr(rec.lead_cand_rules, ctypes.c_uint32, np.uint32, rec.nlead_cands).tolist(),
+                                        arr(rec.lead_cand_starts, ctypes.c_uint64, np.uint64, rec.nlead_cands).tolist()))
+            segs.append(sd)
+        info = {"flags": _result_file_flags(res), "segments": segs, "stats": _lib.result_stats(res)}
+        return findings, _result_candidates(res), info
+    finally:
+        if res:
+            L.tsg_result_free(res)
+        if pin:
+            L.tsg_free_pinned(pin)
+        del d
+
+
+def plan_segments(offsets, resident=False, base=0, with_paths=True, **policy):
+    """The engine's segment planner on an offsets array (tsg_test_plan_segments):
+    one dict per segment (f0, nfiles with the lead, lead, b0, bytes, d_data) plus
+    "lead_bytes".  policy: every field of tsg_segment_policy.  Tests only."""
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    nfiles = len(off) - 1
+    pol = _lib.TsgSegmentPolicy(**policy)
+    cap = max(nfiles, 1)
+    out = (_lib.TsgSegmentInfo * cap)()
+    nout = ctypes.c_uint32()
+    reb = np.zeros(nfiles + 2 * cap + 2, np.uint64)
+    _lib.check(_lib.lib().tsg_test_plan_segments(off.ctypes.data, nfiles, int(resident), base, int(with_paths),
+                                                  ctypes.byref(pol), out, cap, ctypes.byref(nout), reb.ctypes.data,
+                                                  len(reb)))
+    segs, r = [], 0
+    for s in out[:nout.value]:
+        sd = {k: getattr(s, k) for k, _ in s._fields_}
+        sd["lead_bytes"] = int(reb[r + 1]) if s.lead else 0
+        r += s.nfiles + 1
+        segs.append(sd)
+    return segs
+
+
 def prefilter_report(scanner):
     buf = ctypes.c_void_p()
     _lib.check(_lib.lib().tsg_prefilter_report(scanner._rs, ctypes.byref(buf)))
