@@ -158,6 +158,21 @@ int tsg_scan_batch(tsg_engine* e, const uint8_t* data, const uint64_t* offsets, 
 int tsg_scan_batch_resident(tsg_engine* e, const void* d_data, const uint8_t* h_data,
                             const uint64_t* offsets, uint32_t nfiles, const char* const* paths,
                             const uint32_t* path_lens, const uint8_t* binary, tsg_result** out);
+/* The device-only scan: the batch exists only in HBM (the output of
+ * tsg_strip_cr_device, a GPU decompressor, a peer-to-peer read) and no host
+ * copy is passed.  d_data: as for tsg_scan_batch_resident (16-byte aligned,
+ * readable for 16 bytes past the end, on one of the engine's devices);
+ * offsets, paths, path_lens, binary: host arrays as above.  After its second
+ * pass the GPU gathers the files the exact confirmer must read -- those with
+ * candidates or fold-special content; every file when the rule set has a
+ * host-evaluated rule -- into host-mapped memory, and the confirmer runs on
+ * that copy: only those files cross the link.  The result is
+ * tsg_scan_batch_resident's, byte for byte.  TSG_GATHER_CAP (bytes) sets a
+ * gather buffer's first capacity (default: an eighth of a piece + 1 MiB; it
+ * grows on demand). */
+int tsg_scan_batch_device(tsg_engine* e, const void* d_data, const uint64_t* offsets, uint32_t nfiles,
+                          const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
+                          tsg_result** out);
 
 /* Host-feed ceiling: stream `bytes` of host memory (pinned for full rate) to
  * HBM through the engine's upload path in segments, with no kernels; *ms =
@@ -174,7 +189,9 @@ int tsg_feed_probe(tsg_engine* e, const uint8_t* data, uint64_t bytes, double* m
  * d_new_offsets: nfiles + 1 device uint64 receiving each file's start in
  * d_dst.  *out_total = stripped bytes (= d_new_offsets[nfiles]); *ms (may be
  * NULL) = kernel time.  Synchronous.  Binary files (ExtractPrintableBytes)
- * stay on the host path. */
+ * stay on the host path.  The scan to follow it is tsg_scan_batch_device on
+ * d_dst with the host's copy of d_new_offsets (d_dst needs 16 readable bytes
+ * past the stripped total): the stripped bytes never leave the device. */
 int tsg_strip_cr_device(tsg_engine* e, const void* d_src, const uint64_t* d_offsets, uint32_t nfiles,
                         uint64_t total, void* d_dst, uint64_t* d_new_offsets, uint64_t* out_total, double* ms);
 
@@ -191,6 +208,12 @@ int tsg_result_file_error(const tsg_result* r, uint32_t file);
  * UTF-8 bytes are written as \udcXX escapes.  Free with tsg_free. */
 int tsg_result_json(const tsg_result* r, char** json, size_t* len);
 int tsg_result_stats(const tsg_result* r, tsg_stats* out);
+/* What a tsg_scan_batch_device result's gather took (all 0 for the other
+ * scans): files and bytes the GPU placed in host memory for the confirmer,
+ * the runs of adjacent files they formed, the gather kernels' time, and copy
+ * launches repeated with a larger buffer.  Any pointer may be NULL. */
+int tsg_result_gather_stats(const tsg_result* r, uint64_t* files, uint64_t* bytes, uint64_t* runs, double* ms,
+                            uint32_t* retries);
 /* Frees a result; one of >= 4096 files + findings is handed to a background
    thread (its memory returns shortly after the call). */
 void tsg_result_free(tsg_result* r);

@@ -75,6 +75,62 @@ int tsg_test_keep_raw(tsg_engine* e, int on);
 int tsg_result_raw_segments(const tsg_result* r, size_t* n);
 int tsg_result_raw_segment(const tsg_result* r, size_t k, tsg_raw_segment* rec);
 
+/* The device-only scan's gather layout (csrc/gather.h: plan_gather, the CPU
+ * model of gather.hip's device scan) on an offsets array alone: files below
+ * `lead` are never gathered, need[f] != 0 marks a file the confirmer reads,
+ * chunk = the segment's K1 chunk bytes.  goff (nfiles uint64) receives each
+ * file's first byte in the gather buffer or UINT64_MAX; runs (3 uint64 per
+ * run: source in the segment's frame, destination, length; runs_cap runs)
+ * the run table, *nruns its size (set even when it exceeds runs_cap, which
+ * fails), *total the buffer bytes taken.  Tests only. */
+int tsg_test_plan_gather(const uint64_t* offsets, uint32_t nfiles, uint32_t lead, const uint8_t* need, uint32_t chunk,
+                         uint64_t* goff, uint64_t* runs, size_t runs_cap, size_t* nruns, uint64_t* total);
+/* Test hook: while `on`, a tsg_scan_batch_device result keeps, per segment
+ * (in segment order, as tsg_result_raw_segment, whose records it also keeps),
+ * the gather as it came back from the device -- over the segment's files in
+ * its own frame, the lead (if any) as file 0 and offsets counted from the
+ * chunk grid's origin b0 - lead_bytes: need, goff, the run table, the buffer
+ * bytes taken and those bytes; and the buffer's capacity at each
+ * tsg_gather_copy launch with, per launch, whether the 4096-byte 0xA5 pattern
+ * the hook writes past that capacity was still whole afterwards.  While on,
+ * tsg_prefilter_resident called with h_data NULL runs the gather behind its
+ * two passes as well and keeps the one segment's record (no confirmation:
+ * for batches whose confirmation takes long).  Off by default.  No product
+ * entry point calls it. */
+typedef struct {
+  uint32_t nfiles;                 /* the segment's files, the lead included */
+  const uint8_t* need;
+  const uint64_t* goff;
+  const uint64_t* runs;            /* nruns x (source, destination, length) */
+  size_t nruns;
+  uint64_t total;                  /* gather_total */
+  const uint64_t* caps;            /* ncaps capacities, one per copy launch that was waited for */
+  const uint8_t* guard_ok;
+  size_t ncaps;
+  const uint8_t* bytes;            /* total bytes of the gather buffer */
+} tsg_gather_segment;
+int tsg_test_keep_gather(tsg_engine* e, int on);
+int tsg_result_gather_segment(const tsg_result* r, size_t k, tsg_gather_segment* rec);
+/* Test hook: gather buffers the engine's devices own, those back in their
+ * pool (all of them between scans), and their bytes. */
+int tsg_test_gather_pool(tsg_engine* e, uint32_t* buffers, uint32_t* idle, uint64_t* bytes);
+/* CPU model of the device-only scan (tests without a GPU): the table model's
+ * candidates and flags, plan_gather with K1 chunks of `chunk` bytes, the runs
+ * copied into a buffer of exactly the gather's size, and the engine's
+ * confirmation of a segment without a host copy reading that buffer.  The
+ * result carries the findings, the gather stats and one gather record
+ * (tsg_result_gather_segment 0).  Never used by a scan. */
+int tsg_scan_device_model(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* offsets, uint32_t nfiles,
+                          const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
+                          uint32_t chunk, tsg_result** out);
+/* The same; release(user) (may be NULL) is called once the gather is made and
+ * before the confirmation starts: `data` is not read after it, so the caller
+ * may free the batch there -- under a host sanitizer a stray read through the
+ * batch's old address then shows (tools/asan_driver.cpp --device-model). */
+int tsg_scan_device_model_release(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* offsets, uint32_t nfiles,
+                                  const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
+                                  uint32_t chunk, void (*release)(void* user), void* user, tsg_result** out);
+
 /* Bit of a file's flag word (engine.h kFileFoldSpecial): the file holds
  * U+0130, U+212A or U+017F, so the host scans it with the variant tables.  K1
  * may also set it for a file that shares a 16-byte word of the batch with such

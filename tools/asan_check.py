@@ -12,7 +12,9 @@ third run (--parsers) feeds the parsers of untrusted input (layer tars, image
 configs, protobuf messages, an fs tree) with fixtures and truncated /
 mutated copies; a fourth (--concurrency) runs the concurrent host code: the
 per-file queue with 16 callers and with an injected failure, the streamed
-layer / tree pipelines, the result reaper and threaded SecretVec construction.
+layer / tree pipelines, the result reaper and threaded SecretVec construction;
+a fifth (device) runs the CPU model of the device-only scan over the first
+corpus with the batch freed before the confirmation.
 
   python tools/asan_check.py [--mb 8] [--out profiles/r3n_asan.log]
 """
@@ -176,6 +178,9 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--thread", action="store_true", help="ThreadSanitizer instead of ASan + UBSan")
     ap.add_argument("--workdir", default="", help="keep the driver and inputs here")
+    ap.add_argument("--cases", default="c2,c5,parsers,concurrency,device",
+                    help="comma-separated runs: c2, c5, parsers, concurrency, device (the device-only scan's CPU model "
+                         "over the c2 corpus, its batch freed before the confirmation)")
     a = ap.parse_args()
     lines = []
     with (tempfile.TemporaryDirectory() if not a.workdir else _Keep(a.workdir)) as td:
@@ -193,8 +198,10 @@ def main():
                    TSAN_OPTIONS="halt_on_error=1:second_deadlock_stack=1")
         write_parsers_case(os.path.join(td, "parsers"))
         rc_all = 0
-        for case in ("c2", "c5", "parsers", "concurrency"):
-            if case == "parsers":
+        for case in [c for c in a.cases.split(",") if c]:
+            if case == "device":
+                argv = [exe, "--device-model", os.path.join(td, "c2")]
+            elif case == "parsers":
                 argv = [exe, "--parsers", os.path.join(td, case)]
             elif case == "concurrency":      # queue, stream pipelines, reaper, threaded SecretVec
                 argv = [exe, "--concurrency", os.path.join(td, "c2"), os.path.join(td, "parsers")]

@@ -19,6 +19,12 @@
 // and scan threads, small batches), large results freed from several
 // threads at once (the idle-priority reaper) and a table-model result of
 // 70k files (threaded SecretVec construction).
+// with --device-model <case dir>: the CPU model of the device-only scan
+// (tsg_scan_device_model_release, K1 chunks of 512 bytes) over the case's
+// prepared batch, a heap copy of which is freed once the gather is made and
+// before the confirmation starts -- a read through the batch's old address
+// (instead of the exact-size gather buffer) is a use after free; its JSON
+// must be the table model's.
 // The two scan paths must give byte-identical JSON (the superset argument of
 // DESIGN.md §2).  Usage: asan_driver <dir> where <dir> holds config.json
 // (may be empty = builtin rules), data.bin, offsets.bin (uint64 nfiles+1),
@@ -123,6 +129,86 @@ static int run(int argc, char** argv) {
   tsg_free(jm);
   tsg_result_free(host);
   tsg_result_free(model);
+  tsg_prepared_free(prep);
+  tsg_ruleset_free(rs);
+  return same ? 0 : 3;
+}
+
+// The device-only scan's CPU model with the batch freed before confirmation.
+static int run_device_model(const std::string& dir) {
+  const std::string cfg = slurp(dir + "/config.json");
+  const std::string data = slurp(dir + "/data.bin");
+  const std::string offs_raw = slurp(dir + "/offsets.bin");
+  std::vector<uint64_t> offs(offs_raw.size() / 8);
+  std::memcpy(offs.data(), offs_raw.data(), offs.size() * 8);
+  std::vector<std::string> paths;
+  {
+    std::istringstream in(slurp(dir + "/paths.txt"));
+    for (std::string l; std::getline(in, l);) paths.push_back(l);
+  }
+  const uint32_t n = static_cast<uint32_t>(offs.size() - 1);
+  if (paths.size() != n || offs.back() != data.size()) {
+    std::fprintf(stderr, "asan_driver: inconsistent inputs\n");
+    return 2;
+  }
+  std::vector<const char*> pp(n);
+  std::vector<uint32_t> pl(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    pp[i] = paths[i].c_str();
+    pl[i] = static_cast<uint32_t>(paths[i].size());
+  }
+  tsg_ruleset* rs = nullptr;
+  if (tsg_ruleset_compile(cfg.empty() ? nullptr : cfg.c_str(), cfg.size(), &rs) != 0) return fail("ruleset_compile");
+  tsg_prepared* prep = nullptr;
+  if (tsg_prepare_batch(rs, "", reinterpret_cast<const uint8_t*>(data.data()), offs.data(), n, pp.data(), pl.data(), 4,
+                        &prep) != 0)
+    return fail("prepare_batch");
+  const uint8_t* pdata = nullptr;
+  const uint64_t* poffs = nullptr;
+  const uint32_t* pidx = nullptr;
+  const uint8_t* pbin = nullptr;
+  uint32_t nkept = 0;
+  if (tsg_prepared_view(prep, &pdata, &poffs, &pidx, &pbin, &nkept) != 0) return fail("prepared_view");
+  std::vector<const char*> kp(nkept);
+  std::vector<uint32_t> kl(nkept);
+  for (uint32_t k = 0; k < nkept; ++k) {
+    kp[k] = pp[pidx[k]];
+    kl[k] = pl[pidx[k]];
+  }
+  tsg_result* model = nullptr;
+  tsg_result* dev = nullptr;
+  if (tsg_scan_table_model(rs, pdata, poffs, nkept, kp.data(), kl.data(), pbin, &model) != 0)
+    return fail("scan_table_model");
+  // the batch the mode sees: a heap copy of exactly its size, freed by the hook
+  const size_t total = nkept ? poffs[nkept] : 0;
+  uint8_t* batch = static_cast<uint8_t*>(std::malloc(total ? total : 1));
+  std::memcpy(batch, pdata, total);
+  struct Gone { uint8_t* p; bool freed; } gone{batch, false};
+  auto release = [](void* u) {
+    Gone* g = static_cast<Gone*>(u);
+    std::free(g->p);
+    g->freed = true;
+  };
+  if (tsg_scan_device_model_release(rs, batch, poffs, nkept, kp.data(), kl.data(), pbin, 512, release, &gone, &dev) != 0)
+    return fail("scan_device_model_release");
+  if (!gone.freed) { std::fprintf(stderr, "asan_driver: the batch was not released\n"); return 4; }
+  uint64_t gfiles = 0, gbytes = 0, gruns = 0;
+  if (tsg_result_gather_stats(dev, &gfiles, &gbytes, &gruns, nullptr, nullptr) != 0) return fail("gather_stats");
+  char* jm = nullptr;
+  char* jd = nullptr;
+  size_t lm = 0, ld = 0;
+  if (tsg_result_json(model, &jm, &lm) != 0 || tsg_result_json(dev, &jd, &ld) != 0) return fail("result_json");
+  size_t nfind = 0;
+  for (uint32_t k = 0; k < nkept; ++k) nfind += tsg_result_num_findings(dev, k);
+  const bool same = lm == ld && std::memcmp(jm, jd, lm) == 0;
+  std::printf("files %u kept %u bytes %zu findings %zu gathered %llu files %llu bytes %llu runs, batch freed before "
+              "confirmation, device model==table model %s\n", n, nkept, total, nfind,
+              static_cast<unsigned long long>(gfiles), static_cast<unsigned long long>(gbytes),
+              static_cast<unsigned long long>(gruns), same ? "yes" : "NO");
+  tsg_free(jm);
+  tsg_free(jd);
+  tsg_result_free(model);
+  tsg_result_free(dev);
   tsg_prepared_free(prep);
   tsg_ruleset_free(rs);
   return same ? 0 : 3;
@@ -424,6 +510,7 @@ static void* run_thread(void* p) {
   auto* a = static_cast<Args*>(p);
   if (a->argc == 3 && std::string(a->argv[1]) == "--parsers") a->rc = run_parsers(a->argv[2]);
   else if (a->argc == 4 && std::string(a->argv[1]) == "--concurrency") a->rc = run_concurrency(a->argv[2], a->argv[3]);
+  else if (a->argc == 3 && std::string(a->argv[1]) == "--device-model") a->rc = run_device_model(a->argv[2]);
   else a->rc = run(a->argc, a->argv);
   return nullptr;
 }

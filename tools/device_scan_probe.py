@@ -1,0 +1,114 @@
+#!/usr/bin/env python
+"""The device-only scan beside the resident scan on one batch (tooling; not a
+bench.py leg).
+
+  python tools/device_scan_probe.py [--config 1|2] [--gb 1] [--steps 3] [--seed N]
+
+For a config-1-shaped (lognormal source files) or config-2-shaped (log-uniform
+64 B - 64 MB files) batch of workload/synth.py held in HBM it prints one JSON
+line: the resident rate (tsg_scan_batch_resident, with the host copy), the
+device-only rate (tsg_scan_batch_device, without), whether the findings are
+equal, the gather's files / bytes / runs / kernel ms, and the time of one
+hipMemcpyAsync of gather_bytes from device memory into pinned host memory on
+the same box -- the yardstick for the gather's direct stores."""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from trivy_amd import _lib  # noqa: E402
+from trivy_amd import secret as S  # noqa: E402
+from workload import synth  # noqa: E402
+
+
+def d2h_copy_ms(nbytes, reps=5):
+    """One async D2H copy of nbytes from device memory into pinned memory: best of reps, ms."""
+    if nbytes == 0:
+        return 0.0
+    src = torch.empty(nbytes, dtype=torch.uint8, device="cuda:0")
+    dst = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+    best = None
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        dst.copy_(src, non_blocking=True)
+        b.record()
+        b.synchronize()
+        ms = a.elapsed_time(b)
+        best = ms if best is None else min(best, ms)
+    return best
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", type=int, default=1, choices=[1, 2])
+    ap.add_argument("--gb", type=float, default=1.0)
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=0x71215EC7)
+    a = ap.parse_args()
+    L = _lib.lib()
+    corpus = synth.generate(int(a.gb * 1e9), seed=a.seed, sizes="lognormal" if a.config == 1 else "loguniform")
+    nfiles, nbytes = len(corpus.paths), corpus.nbytes
+    data = corpus.data
+    off = np.ascontiguousarray(corpus.offsets, dtype=np.uint64)
+    d = torch.from_numpy(data).to("cuda:0")
+    torch.cuda.synchronize()
+    sc = S.Scanner(None)
+    eng = sc.engine()
+    paths, lens, _keep = _lib.pack_paths(corpus.paths)
+
+    def scan(device_only):
+        res = ctypes.c_void_p()
+        t0 = time.perf_counter()
+        if device_only:
+            _lib.check(L.tsg_scan_batch_device(eng, ctypes.c_void_p(d.data_ptr()), off.ctypes.data, nfiles, paths,
+                                               lens, None, ctypes.byref(res)))
+        else:
+            _lib.check(L.tsg_scan_batch_resident(eng, ctypes.c_void_p(d.data_ptr()), data.ctypes.data, off.ctypes.data,
+                                                 nfiles, paths, lens, None, ctypes.byref(res)))
+        return res, (time.perf_counter() - t0) * 1e3
+
+    out = {}
+    for name, dev in (("resident", False), ("device_only", True)):
+        times, js, st, gs = [], None, None, None
+        for k in range(a.steps + 1):                    # the first step warms the lanes and buffers up
+            res, ms = scan(dev)
+            if k:
+                times.append(ms)
+            if k == a.steps:
+                js = _lib.result_json(res)
+                st = _lib.result_stats(res)
+                gs = _lib.result_gather_stats(res)
+            L.tsg_result_free(res)
+        out[name] = (times, js, st, gs)
+    tr, jr, sr, _ = out["resident"]
+    td, jd, sd, gd = out["device_only"]
+    copy_ms = d2h_copy_ms(int(gd["gather_bytes"]))
+    gb = nbytes / 1e9
+    line = {
+        "probe": "device_scan", "config": a.config, "bytes": nbytes, "files": nfiles, "steps": a.steps,
+        "resident_ms": [round(x, 3) for x in tr], "device_only_ms": [round(x, 3) for x in td],
+        "resident_gbps": round(gb / (min(tr) / 1e3), 1), "device_only_gbps": round(gb / (min(td) / 1e3), 1),
+        "findings_equal": jr == jd, "findings": int(sd["findings"]),
+        "confirm_files": int(sd["confirm_files"]), "pieces": int(sd["pieces"]),
+        "gather_files": gd["gather_files"], "gather_bytes": gd["gather_bytes"], "gather_runs": gd["gather_runs"],
+        "gather_ms": round(gd["gather_ms"], 3), "gather_retries": gd["gather_retries"],
+        "gather_share_of_batch": round(gd["gather_bytes"] / max(nbytes, 1), 4),
+        "gather_gbps": round(gd["gather_bytes"] / 1e6 / gd["gather_ms"], 1) if gd["gather_ms"] else None,
+        "d2h_copy_ms": round(copy_ms, 3),
+        "d2h_copy_gbps": round(gd["gather_bytes"] / 1e6 / copy_ms, 1) if copy_ms else None,
+        "gather_over_copy": round(gd["gather_ms"] / copy_ms, 2) if copy_ms else None,
+    }
+    print(json.dumps(line), flush=True)
+    return 0 if line["findings_equal"] else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -44,6 +44,13 @@ class TsgRawSegment(ctypes.Structure):
                 ("nlead_cands", ctypes.c_size_t)]
 
 
+class TsgGatherSegment(ctypes.Structure):
+    _fields_ = [("nfiles", ctypes.c_uint32), ("need", ctypes.c_void_p), ("goff", ctypes.c_void_p),
+                ("runs", ctypes.c_void_p), ("nruns", ctypes.c_size_t), ("total", ctypes.c_uint64),
+                ("caps", ctypes.c_void_p), ("guard_ok", ctypes.c_void_p), ("ncaps", ctypes.c_size_t),
+                ("bytes", ctypes.c_void_p)]
+
+
 class TsgStats(ctypes.Structure):
     _fields_ = [("k1_ms", ctypes.c_double), ("k2_ms", ctypes.c_double), ("h2d_ms", ctypes.c_double),
                 ("d2h_ms", ctypes.c_double), ("host_ms", ctypes.c_double), ("total_ms", ctypes.c_double),
@@ -82,6 +89,26 @@ SIGNATURES = [
     ("tsg_scan_batch_resident", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                 ctypes.c_uint32, c_char_pp, ctypes.c_void_p, ctypes.c_void_p,
                                                 ctypes.POINTER(ctypes.c_void_p)]),
+    ("tsg_scan_batch_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                              c_char_pp, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.POINTER(ctypes.c_void_p)]),
+    ("tsg_result_gather_stats", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
+                                                ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                                ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint32)]),
+    ("tsg_test_plan_gather", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                             ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                             ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint64)]),
+    ("tsg_test_keep_gather", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    ("tsg_result_gather_segment", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(TsgGatherSegment)]),
+    ("tsg_test_gather_pool", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
+                                             ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)]),
+    ("tsg_scan_device_model", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                              c_char_pp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                              ctypes.POINTER(ctypes.c_void_p)]),
+    ("tsg_scan_device_model_release", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                      c_char_pp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                      ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.POINTER(ctypes.c_void_p)]),
     ("tsg_prefilter_resident", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]),
     ("tsg_feed_probe", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
@@ -311,6 +338,16 @@ def result_stats(res):
     st = TsgStats()
     check(lib().tsg_result_stats(res, ctypes.byref(st)))
     return {k: getattr(st, k) for k, _ in TsgStats._fields_}
+
+
+def result_gather_stats(res):
+    """What a tsg_scan_batch_device result's gather took (tsg_result_gather_stats)."""
+    files, nbytes, runs = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    ms, retries = ctypes.c_double(), ctypes.c_uint32()
+    check(lib().tsg_result_gather_stats(res, ctypes.byref(files), ctypes.byref(nbytes), ctypes.byref(runs),
+                                        ctypes.byref(ms), ctypes.byref(retries)))
+    return {"gather_files": files.value, "gather_bytes": nbytes.value, "gather_runs": runs.value,
+            "gather_ms": ms.value, "gather_retries": retries.value}
 
 
 def pack_paths(paths):

@@ -200,8 +200,9 @@ void tsg_free_pinned(void* p);
 
 static int do_scan(tsg_engine* e, const void* d_data, const uint8_t* h_data, const uint64_t* offsets,
                    uint32_t nfiles, const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
-                   tsg_result** out) {
-  if (!e || !out || !offsets || (nfiles && !paths) || (!h_data && nfiles)) return fail(TSG_ERR_INVALID, "NULL argument");
+                   tsg_result** out, bool device_only = false) {
+  if (!e || !out || !offsets || (nfiles && !paths) || (!h_data && nfiles && !device_only))
+    return fail(TSG_ERR_INVALID, "NULL argument");
   BatchInput in;
   in.h_data = h_data;
   in.d_data = d_data;
@@ -213,7 +214,7 @@ static int do_scan(tsg_engine* e, const void* d_data, const uint8_t* h_data, con
   auto* r = new tsg_result();
   r->rs = e->eng->ruleset();
   std::string err;
-  if (!e->eng->keep_raw()) {
+  if (!e->eng->keep_raw() && !(device_only && e->eng->keep_gather())) {
     if (!e->eng->scan(in, &r->files, &r->stats, &err)) { delete r; return fail(TSG_ERR_HIP, err); }
   } else {
     // test hook (tsg_test_keep_raw): the segments' GPU outputs beside the findings
@@ -243,6 +244,28 @@ int tsg_scan_batch_resident(tsg_engine* e, const void* d_data, const uint8_t* h_
   TSG_API_CATCH
 }
 
+int tsg_scan_batch_device(tsg_engine* e, const void* d_data, const uint64_t* offsets, uint32_t nfiles,
+                          const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
+                          tsg_result** out) {
+  TSG_API_TRY
+  if (!d_data) return fail(TSG_ERR_INVALID, "d_data is NULL");
+  return do_scan(e, d_data, nullptr, offsets, nfiles, paths, path_lens, binary, out, /*device_only=*/true);
+  TSG_API_CATCH
+}
+
+int tsg_result_gather_stats(const tsg_result* r, uint64_t* files, uint64_t* bytes, uint64_t* runs, double* ms,
+                            uint32_t* retries) {
+  TSG_API_TRY
+  if (!r) return fail(TSG_ERR_INVALID, "result is NULL");
+  if (files) *files = r->stats.gather_files;
+  if (bytes) *bytes = r->stats.gather_bytes;
+  if (runs) *runs = r->stats.gather_runs;
+  if (ms) *ms = r->stats.gather_ms;
+  if (retries) *retries = r->stats.gather_retries;
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
 int tsg_prefilter_resident(tsg_engine* e, const void* d_data, const uint8_t* h_data, const uint64_t* offsets,
                            uint32_t nfiles, tsg_result** out) {
   TSG_API_TRY
@@ -259,6 +282,10 @@ int tsg_prefilter_resident(tsg_engine* e, const void* d_data, const uint8_t* h_d
   r->chunk_nl = std::move(raw.nl);
   r->nl_chunk = raw.chunk;
   r->file_flags = std::move(raw.ff);
+  if (!raw.gather.goff.empty() || !raw.gather.gather_caps.empty()) {   // tsg_test_keep_gather, h_data NULL
+    r->raw_segs.resize(1);
+    r->raw_segs[0] = std::move(raw.gather);
+  }
   r->files.resize(nfiles);
   *out = r;
   return TSG_OK;
@@ -896,6 +923,97 @@ int tsg_test_keep_raw(tsg_engine* e, int on) {
   TSG_API_TRY
   if (!e) return fail(TSG_ERR_INVALID, "engine is NULL");
   e->eng->set_keep_raw(on != 0);
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_test_keep_gather(tsg_engine* e, int on) {
+  TSG_API_TRY
+  if (!e) return fail(TSG_ERR_INVALID, "engine is NULL");
+  e->eng->set_keep_gather(on != 0);
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_result_gather_segment(const tsg_result* r, size_t k, tsg_gather_segment* rec) {
+  TSG_API_TRY
+  if (!r || !rec) return fail(TSG_ERR_INVALID, "NULL argument");
+  if (k >= r->raw_segs.size()) return fail(TSG_ERR_INVALID, "no such segment");
+  const RawSegment& s = r->raw_segs[k];
+  static_assert(sizeof(GatherRun) == 3 * sizeof(uint64_t), "tsg_gather_segment::runs is GatherRun's three uint64");
+  rec->nfiles = static_cast<uint32_t>(s.goff.size());
+  rec->need = s.need.data();
+  rec->goff = s.goff.data();
+  rec->runs = reinterpret_cast<const uint64_t*>(s.runs.data());
+  rec->nruns = s.runs.size();
+  rec->total = s.gather_total;
+  rec->caps = s.gather_caps.data();
+  rec->guard_ok = s.guard_ok.data();
+  rec->ncaps = s.gather_caps.size();
+  rec->bytes = s.gathered.data();
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_test_gather_pool(tsg_engine* e, uint32_t* buffers, uint32_t* idle, uint64_t* bytes) {
+  TSG_API_TRY
+  if (!e || !buffers || !idle || !bytes) return fail(TSG_ERR_INVALID, "NULL argument");
+  e->eng->gather_pool(buffers, idle, bytes);
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_test_plan_gather(const uint64_t* offsets, uint32_t nfiles, uint32_t lead, const uint8_t* need, uint32_t chunk,
+                         uint64_t* goff, uint64_t* runs, size_t runs_cap, size_t* nruns, uint64_t* total) {
+  TSG_API_TRY
+  if (!offsets || !need || !goff || !nruns || !total || chunk == 0 || lead > nfiles)
+    return fail(TSG_ERR_INVALID, "bad argument");
+  for (uint32_t i = 0; i < nfiles; ++i)
+    if (offsets[i + 1] < offsets[i]) return fail(TSG_ERR_INVALID, "offsets must be non-decreasing");
+  GatherPlan gp;
+  plan_gather(offsets, nfiles, lead, need, chunk, &gp);
+  std::copy(gp.goff.begin(), gp.goff.end(), goff);
+  *nruns = gp.runs.size();
+  *total = gp.total;
+  if (gp.runs.size() > runs_cap || (!runs && !gp.runs.empty())) return fail(TSG_ERR_INVALID, "run table too small");
+  for (size_t k = 0; k < gp.runs.size(); ++k) {
+    runs[3 * k] = gp.runs[k].src; runs[3 * k + 1] = gp.runs[k].dst; runs[3 * k + 2] = gp.runs[k].len;
+  }
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_scan_device_model(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* offsets, uint32_t nfiles,
+                          const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
+                          uint32_t chunk, tsg_result** out) {
+  return tsg_scan_device_model_release(rs, data, offsets, nfiles, paths, path_lens, binary, chunk, nullptr, nullptr, out);
+}
+
+int tsg_scan_device_model_release(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* offsets, uint32_t nfiles,
+                                  const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
+                                  uint32_t chunk, void (*release)(void* user), void* user, tsg_result** out) {
+  TSG_API_TRY
+  if (!rs || !out || !offsets || (nfiles && (!paths || !data)) || chunk == 0) return fail(TSG_ERR_INVALID, "NULL argument");
+  std::string err;
+  // an engine without devices for this call, around the models' compiled prefilter
+  const std::shared_ptr<const Prefilter> pfp = model_prefilter(rs->rs, &err);
+  if (!pfp) return fail(TSG_ERR_INTERNAL, err);
+  const std::unique_ptr<Engine> eng = Engine::create_model(rs->rs, *pfp);
+  BatchInput in;
+  in.h_data = data ? data : reinterpret_cast<const uint8_t*>("");
+  in.offsets = offsets;
+  in.nfiles = nfiles;
+  in.paths = paths;
+  in.path_lens = path_lens;
+  in.binary = binary;
+  std::unique_ptr<tsg_result> r(new tsg_result());
+  r->rs = rs->rs;
+  RawScan raw;
+  const std::function<void()> before_confirm = [&] { if (release) release(user); };
+  if (!eng->model_scan_device(in, chunk, &r->files, &r->stats, &err, &raw, &before_confirm))
+    return fail(TSG_ERR_INTERNAL, err);
+  r->raw_segs = std::move(raw.segs);
+  *out = r.release();
   return TSG_OK;
   TSG_API_CATCH
 }

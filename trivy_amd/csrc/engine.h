@@ -12,10 +12,14 @@
 #include <thread>
 #include <vector>
 
+#include "gather.h"
 #include "prefilter.h"
 #include "scanner.h"
 #include "segments.h"
 #include "wirepack.h"
+#ifdef __HIPCC__
+#include "gather_dev.h"                 // (the engine's own translation unit: the gather kernels' launches)
+#endif
 
 namespace tsg {
 
@@ -33,18 +37,18 @@ struct ScanStats {
   uint64_t wire_bytes = 0;
   uint32_t packed_strips = 0, raw_strips = 0;
   double pack_ms = 0;
+  // device-only scans (gather.h): files, bytes and runs the GPU gathered for
+  // the confirmer, the gather kernels' time, copy launches repeated with a
+  // larger buffer
+  uint64_t gather_files = 0, gather_bytes = 0, gather_runs = 0;
+  double gather_ms = 0;
+  uint32_t gather_retries = 0;
 };
 
 // A batch scan stage: results[i] = Scan(ScanArgs{paths[i], data[off[i]:off[i+1]],
 // binary[i]}) -- Engine::scan, or (tests only) the CPU model of its passes.
 using BatchScanFn = std::function<bool(const BatchInput& in, SecretVec* results, std::string* err)>;
 
-// K1's per-chunk and per-file outputs of one prefilter_only call (tests).
-struct PrefilterRaw {
-  std::vector<uint16_t> nl;             // '\n' count per K1 chunk of the packed batch
-  std::vector<uint32_t> ff;             // per-file flag word (kFileFoldSpecial)
-  uint32_t chunk = 0;                   // K1 chunk bytes (nl[] granularity)
-};
 // Per-file flag word K1 writes (fflags): bit 0 = the file holds U+0130, U+212A
 // or U+017F, whose lower / upper case is ASCII (the host re-scans it exactly);
 // also set for a file that shares a 16-byte word of the batch with such a
@@ -64,6 +68,24 @@ struct RawSegment {
   uint32_t lead_emitted = 0;            // candidates K2 emitted for the lead (duplicates included)
   std::vector<uint32_t> lead_rules;     // the lead's distinct candidates, sorted by (rule, start)
   std::vector<uint64_t> lead_starts;
+  // device-only scans with tsg_test_keep_gather on: the gather as it came back
+  // from the device, over the segment's files with the lead (segment frame)
+  std::vector<uint8_t> need;
+  std::vector<uint64_t> goff;
+  std::vector<GatherRun> runs;
+  uint64_t gather_total = 0;
+  std::vector<uint64_t> gather_caps;    // the buffer's capacity at each copy launch
+  std::vector<uint8_t> guard_ok;        // per launch: the 0xA5 pattern past that capacity was still whole
+  std::vector<uint8_t> gathered;        // gather_total bytes of the buffer
+};
+// K1's per-chunk and per-file outputs of one prefilter_only call (tests).
+struct PrefilterRaw {
+  std::vector<uint16_t> nl;             // '\n' count per K1 chunk of the packed batch
+  std::vector<uint32_t> ff;             // per-file flag word (kFileFoldSpecial)
+  uint32_t chunk = 0;                   // K1 chunk bytes (nl[] granularity)
+  // tsg_test_keep_gather on and no host copy given: the device-only scan's
+  // gather of this one segment (need ... gathered), without a confirmation
+  RawSegment gather;
 };
 struct RawScan {
   std::vector<RawSegment> segs;
@@ -102,7 +124,8 @@ class Engine {
   // Only the two GPU passes (no host confirmation): used by tests to compare
   // raw candidates ([file][rule], exclude-block pseudo-rules after the rules,
   // as in Prefilter::rules).  Resident data on the engine's first device.
-  // raw (optional): K1's other outputs as they came back from the device.
+  // raw (optional): K1's other outputs as they came back from the device
+  // (and, with tsg_test_keep_gather on and no in.h_data, the gather's).
   bool prefilter_only(const BatchInput& in, std::vector<std::vector<std::vector<uint64_t>>>* cands,
                       ScanStats* stats, std::string* err, PrefilterRaw* raw = nullptr);
 
@@ -125,6 +148,23 @@ class Engine {
   // Test hook (tsg_test_keep_raw): the C-ABI's scans pass a RawScan while it is on.
   void set_keep_raw(bool on) { keep_raw_.store(on); }
   bool keep_raw() const { return keep_raw_.load(std::memory_order_relaxed); }
+  // Test hook (tsg_test_keep_gather): with keep_raw's record, a device-only
+  // scan keeps each segment's gather (RawSegment::need ... gathered).
+  void set_keep_gather(bool on) { keep_gather_.store(on); }
+  bool keep_gather() const { return keep_gather_.load(std::memory_order_relaxed); }
+  // Test hook: gather buffers the devices' pools own, those back in a pool, their bytes.
+  void gather_pool(uint32_t* buffers, uint32_t* idle, uint64_t* bytes);
+  // CPU model of a device-only scan (tests without a GPU): an engine without
+  // devices around a compiled prefilter (copied), and one batch through the table model's candidates, plan_gather,
+  // a memcpy gather into a buffer of its own and confirm_segment without
+  // h_data.  in.h_data is the batch (read only to build the model's GPU
+  // outputs and the gather); chunk: the K1 chunk to model.
+  static std::unique_ptr<Engine> create_model(std::shared_ptr<const Ruleset> rs, const Prefilter& pf);
+  // before_confirm (optional) runs once the gather is made and before the
+  // confirmation: nothing reads in.h_data after it (a sanitizer run frees the
+  // batch there).
+  bool model_scan_device(const BatchInput& in, uint32_t chunk, SecretVec* results, ScanStats* stats, std::string* err,
+                         RawScan* raw = nullptr, const std::function<void()>* before_confirm = nullptr);
 
   const Prefilter& prefilter() const { return pf_; }
   std::shared_ptr<const Ruleset> ruleset() const { return rs_; }
@@ -141,7 +181,8 @@ class Engine {
   // (used by this call only: nothing of it stays on the pooled lane)
   bool run_segment(DeviceTables& dt, Lane& ln, const Segment& sg, const void* d_data, const uint64_t* d_off_up,
                    ScanStats* st, GpuOut* out, std::string* err, const std::function<void()>* while_gpu = nullptr,
-                   K1Chain* chain = nullptr, bool defer_copy = false, const StageIn* stage = nullptr);
+                   K1Chain* chain = nullptr, bool defer_copy = false, const StageIn* stage = nullptr,
+                   bool gather = false);
   // run_segment's phases (SegRun: what they share)
   bool seg_geometry(SegRun& r, GpuOut* out, std::string* err);
   bool seg_stage_offsets(SegRun& r, std::string* err);
@@ -151,6 +192,10 @@ class Engine {
   bool seg_launch_k1(SegRun& r, int attempt, std::string* err);
   bool seg_launch_k2(SegRun& r, int a2, std::string* err);
   bool seg_readback_wait(SegRun& r, int a2, std::string* err);
+  bool seg_wait(SegRun& r, std::string* err);
+  // device-only scans: the gather kernels behind K2, and the copy again into a larger buffer
+  bool seg_launch_gather(SegRun& r, GpuOut* out, std::string* err);
+  bool seg_gather_retry(SegRun& r, GpuOut* out, std::string* err);
   void seg_hand_off(SegRun& r, uint32_t ncands, uint32_t nover, bool defer_copy, GpuOut* out);
   bool seg_write_traces(SegRun& r, std::string* err);   // (probe library)
   bool fold_k2_stats(Lane& ln, std::string* err);
@@ -229,6 +274,9 @@ class Engine {
   bool host_profile_ = false;           // TSG_HOST_PROFILE=1: per-segment host confirm breakdown on stderr
   std::atomic<uint32_t> inject_fail_{0};
   std::atomic<bool> keep_raw_{false};
+  std::atomic<bool> keep_gather_{false};
+  uint64_t cand_cap0_ = 0;              // a fresh lane's candidate capacity (TSG_CAND_CAP); 0 = the lane's default
+  uint64_t gather_cap_ = 0;             // a gather buffer's first capacity in bytes (TSG_GATHER_CAP); 0 = bytes / 8 + 1 MiB
   std::mutex k2s_mu_;
   std::vector<unsigned long long> k2s_;  // 4 per rule: hits, past the keyword gate, verify starts, bytes walked
   SegmentPolicy seg_;                   // where a batch is cut (segments.h: TSG_PIECES, TSG_SEGMENT_BYTES, ...)

@@ -1428,6 +1428,8 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
 
 }  // namespace
 
+struct GatherBuf;
+
 // Device tables of one scan DFA group (one K1 launch per group).
 struct K1Group {
   DevBuf<uint16_t> next;       // pre-multiplied uint16 row offsets, row stride `stride`
@@ -1455,6 +1457,9 @@ struct DeviceTables {
   std::vector<std::pair<const void*, int>> lds_set;   // K1 builds whose dynamic-LDS limit is set (per device)
   std::vector<std::unique_ptr<Lane>> lanes;
   std::vector<Lane*> free_lanes;
+  // device-only scans: the pool of gather buffers (GatherLease)
+  std::vector<std::unique_ptr<GatherBuf>> gather_bufs;
+  std::vector<GatherBuf*> gather_idle;
   ~DeviceTables();
 };
 
@@ -1490,6 +1495,59 @@ struct PinnedBuf {
   bool ensure_offsets(size_t nfiles, std::string* err) {
     return ensure((nfiles + 1) * sizeof(uint64_t), hipHostMallocDefault, err);
   }
+};
+
+// A device-only scan's gather destination: host-mapped, coherent pinned
+// memory tsg_gather_copy stores into (mem.cap = its capacity; kGatherGuard
+// more bytes follow, which no launch may touch: tsg_test_keep_gather checks).
+// It belongs to its device's pool and travels with a segment's GpuOut from the
+// driver that filled it to the end of that segment's confirmation -- which
+// runs while the driver's lane is already pieces further on, so it cannot be
+// one of the lane's own buffers as the small readback buffers are.
+constexpr size_t kGatherGuard = 4096;
+struct GatherBuf { PinnedBuf mem; };
+struct GatherLease {
+  DeviceTables* dt = nullptr;
+  GatherBuf* b = nullptr;
+  GatherLease() = default;
+  GatherLease(const GatherLease&) = delete;
+  GatherLease& operator=(const GatherLease&) = delete;
+  ~GatherLease() { release(); }
+  // a buffer of at least `bytes` out of dt's pool (grown or created if none is large enough)
+  bool take(DeviceTables& d, size_t bytes, std::string* err) {
+    release();
+    {
+      std::lock_guard<std::mutex> lk(d.mu);
+      auto& idle = d.gather_idle;
+      const size_t none = idle.size();
+      size_t fit = none, big = none;                 // the smallest that fits, else the largest
+      for (size_t k = 0; k < idle.size(); ++k) {
+        const size_t c = idle[k]->mem.cap;
+        if (c >= bytes && (fit == none || c < idle[fit]->mem.cap)) fit = k;
+        if (big == none || c > idle[big]->mem.cap) big = k;
+      }
+      const size_t pick = fit != none ? fit : big;
+      if (pick < idle.size()) {
+        b = idle[pick];
+        idle.erase(idle.begin() + pick);
+      } else {
+        d.gather_bufs.emplace_back(new GatherBuf());
+        b = d.gather_bufs.back().get();
+      }
+    }
+    dt = &d;
+    // (exact size: a test sets a capacity of 256 bytes and expects the retry)
+    if (!b->mem.ensure(bytes, hipHostMallocMapped | hipHostMallocCoherent, err, kGatherGuard)) { release(); return false; }
+    return true;
+  }
+  void release() {
+    if (!b) return;
+    std::lock_guard<std::mutex> lk(dt->mu);
+    dt->gather_idle.push_back(b);
+    b = nullptr;
+  }
+  uint8_t* host() const { return b ? b->mem.as<uint8_t>() : nullptr; }
+  size_t cap() const { return b ? b->mem.cap : 0; }
 };
 
 // Readbacks of one segment: dwords of device buffers into host-mapped
@@ -1562,8 +1620,10 @@ struct LaneStreams {
   hipStream_t unpack = nullptr;
   hipEvent_t wire_raw_ev[4] = {};
   hipEvent_t wire_copies_done[2] = {};
+  hipEvent_t gev[2] = {};                       // device-only scans: the gather kernels' start / end (compute stream)
   ~LaneStreams() {
     for (hipEvent_t* e : {&ev[0], &ev[1], &ev[2], &ev[3], &ev_sync, &up_begin[0], &up_begin[1], &up_done[0], &up_done[1],
+                          &gev[0], &gev[1],
                           &anchor, &wire_raw_ev[0], &wire_raw_ev[1], &wire_raw_ev[2], &wire_raw_ev[3],
                           &wire_copies_done[0], &wire_copies_done[1]})
       if (*e) (void)hipEventDestroy(*e);
@@ -1608,6 +1668,14 @@ struct Lane : LaneStreams {
   DevBuf<unsigned long long> d_k2s;    // TSG_K2_STATS: per-rule K2 counters (4 per rule)
   DevBuf<unsigned int> d_cnt;
   DevBuf<uint8_t> d_cr;                // CR strip scratch (crstrip.hip)
+  // device-only scans (gather.hip): per-file need flags and gather offsets,
+  // the run table, [runs, gather_total]; their readbacks; the gather buffer
+  // size the lane's last segment ended with
+  DevBuf<uint8_t> d_need;
+  DevBuf<uint64_t> d_goff, d_gmeta;
+  DevBuf<GatherRun> d_gruns;
+  PinnedBuf rb_need, rb_goff, rb_gruns, rb_gmeta;
+  size_t gather_cap = 0;
   size_t hit_cap = 1 << 20, cand_cap = 1 << 18, over_cap = 1 << 18;
   double k2_maxr_per_byte = 0;                       // K2 grid of the next segment: the last one's fullest region
   uint64_t k2_over_est = 0;                          // per byte, and its overflow hit count
@@ -1631,11 +1699,33 @@ struct GpuOut {
   const uint16_t* rb_nl = nullptr;
   size_t n_cands = 0, n_ff = 0, n_nl = 0;
   bool deferred = false;
+  // device-only scans: the gather buffer (its lease ends with this record,
+  // after the confirmation), where each file's bytes are in it, and what the
+  // gather took; need / gruns / caps / guard_ok only with tsg_test_keep_gather.
+  // gbase: the buffer's host address (the CPU model sets one of its own).
+  GatherLease gather;
+  const uint8_t* gbase = nullptr;
+  bool gathered = false;
+  uint64_t gather_total = 0, gather_files = 0;
+  std::vector<uint64_t> goff;
+  std::vector<uint8_t> need;
+  std::vector<GatherRun> gruns;
+  std::vector<uint64_t> gather_caps;
+  std::vector<uint8_t> guard_ok;
+  const uint64_t* rb_goff = nullptr;
+  const uint8_t* rb_need = nullptr;
+  const GatherRun* rb_gruns = nullptr;
+  size_t n_goff = 0, n_need = 0, n_gruns = 0;
   void finish_copy() {
     if (!deferred) return;
     cands.assign(rb_cands, rb_cands + n_cands);
     ff.assign(rb_ff, rb_ff + n_ff);
     nl.assign(rb_nl, rb_nl + n_nl);
+    if (gathered) {
+      goff.assign(rb_goff, rb_goff + n_goff);
+      need.assign(rb_need, rb_need + n_need);
+      gruns.assign(rb_gruns, rb_gruns + n_gruns);
+    }
     deferred = false;
   }
   // the confirmation's plan (plan_confirm): candidates grouped per file, the
@@ -1930,6 +2020,8 @@ void add_stats(ScanStats* a, const ScanStats& s) {
   a->table_in_lds = s.table_in_lds;
   a->wire_bytes += s.wire_bytes; a->packed_strips += s.packed_strips; a->raw_strips += s.raw_strips;
   a->pack_ms += s.pack_ms;
+  a->gather_bytes += s.gather_bytes; a->gather_runs += s.gather_runs; a->gather_ms += s.gather_ms;
+  a->gather_retries += s.gather_retries;
 }
 
 }  // namespace
@@ -1975,6 +2067,8 @@ std::unique_ptr<Engine> Engine::create(std::shared_ptr<const Ruleset> rs, const 
     if (v >= kWireBlock) e->wire_strip_ = std::min<uint64_t>(static_cast<uint64_t>(v) / kWireBlock * kWireBlock, kWireMaxStrip);
   }
   if (e->host_profile_) g_scan_prof_on.store(true, std::memory_order_relaxed);
+  env_int("TSG_GATHER_CAP", 256, INT64_MAX, &e->gather_cap_);   // (from 256 bytes: tests force the capacity retry)
+  env_int("TSG_CAND_CAP", 16, INT64_MAX, &e->cand_cap0_);       // (tests force K2's candidate-overflow retry on small batches)
   env_int("TSG_K1_TAIL_ROUNDS", 0, 16, &e->k1_tail_rounds_);
   if (const char* c = std::getenv("TSG_K1_TOP8")) e->k1_top8_ = std::max(0, std::min(2, std::atoi(c)));
   env_int("TSG_K2_HITS_PER_THREAD", 1, 64, &e->k2_hits_per_thread_);
@@ -2035,6 +2129,7 @@ Lane* Engine::acquire_lane(DeviceTables& dt, std::string* err) {
   }
   std::unique_ptr<Lane> l(new Lane());
   l->device = dt.device;
+  if (cand_cap0_) l->cand_cap = cand_cap0_;
   if (hipSetDevice(dt.device) != hipSuccess || hipStreamCreateWithFlags(&l->compute, hipStreamNonBlocking) != hipSuccess ||
       hipStreamCreateWithFlags(&l->copy, hipStreamNonBlocking) != hipSuccess ||
       !l->d_cnt.ensure(kCntBytes / sizeof(unsigned int), err)) {
@@ -2093,6 +2188,104 @@ void Engine::footprint(uint32_t* lanes, uint32_t* calls, uint32_t* pool_threads)
   for (auto& c : calls_) if (c->pool) *pool_threads += static_cast<uint32_t>(c->pool->size());
 }
 
+void Engine::gather_pool(uint32_t* buffers, uint32_t* idle, uint64_t* bytes) {
+  *buffers = *idle = 0;
+  *bytes = 0;
+  for (auto& d : dev_) {
+    std::lock_guard<std::mutex> lk(d->mu);
+    *buffers += static_cast<uint32_t>(d->gather_bufs.size());
+    *idle += static_cast<uint32_t>(d->gather_idle.size());
+    for (auto& b : d->gather_bufs) *bytes += b->mem.cap;
+  }
+}
+
+std::unique_ptr<Engine> Engine::create_model(std::shared_ptr<const Ruleset> rs, const Prefilter& pf) {
+  std::unique_ptr<Engine> e(new Engine());
+  e->rs_ = std::move(rs);
+  e->pf_ = pf;
+  return e;
+}
+
+bool Engine::model_scan_device(const BatchInput& in, uint32_t chunk, SecretVec* results, ScanStats* st, std::string* err,
+                               RawScan* raw, const std::function<void()>* before_confirm) {
+  if (!in.h_data || !in.offsets || !in.paths || chunk == 0) { *err = "model_scan_device: NULL argument"; return false; }
+  const uint32_t nfiles = in.nfiles;
+  const uint64_t total = nfiles ? in.offsets[nfiles] : 0;
+  // the GPU passes' outputs as the table model gives them: candidates, file
+  // flags, '\n' per chunk
+  GpuOut g;
+  g.chunk = chunk;
+  g.ff.assign(nfiles, 0);
+  g.nl.assign((total + chunk - 1) / chunk, 0);
+  for (uint64_t x = 0; x < total; ++x) g.nl[x / chunk] += in.h_data[x] == '\n';
+  bool all = false;
+  for (const auto& pr : pf_.rules) all = all || pr.mode == 1;
+  std::vector<uint8_t> need(nfiles, 0);
+  for (uint32_t f = 0; f < nfiles; ++f) {
+    std::vector<std::vector<uint64_t>> cand;
+    std::vector<uint8_t> gate;
+    if (prefilter_reference_file(pf_, in.h_data + in.offsets[f], in.offsets[f + 1] - in.offsets[f], &cand, &gate))
+      g.ff[f] = kFileFoldSpecial;
+    for (size_t r = 0; r < cand.size(); ++r)
+      for (uint64_t s : cand[r]) g.cands.push_back(CandDev{f, static_cast<uint32_t>(r), s});
+    need[f] = all || g.ff[f] || std::any_of(cand.begin(), cand.end(), [](const std::vector<uint64_t>& v) { return !v.empty(); });
+  }
+  // the gather: plan_gather's layout, the runs copied byte for byte into a
+  // buffer of exactly gather_total bytes (so a read outside a run is a read
+  // outside an allocation)
+  GatherPlan gp;
+  plan_gather(in.offsets, nfiles, 0, need.data(), chunk, &gp);
+  std::vector<uint8_t> buf(gp.total);
+  for (const GatherRun& r : gp.runs) std::memcpy(buf.data() + r.dst, in.h_data + r.src, r.len);
+  g.gbase = buf.data();
+  g.gathered = true;
+  g.gather_total = gp.total;
+  g.goff = gp.goff;
+  // the confirmation of a device-only segment: no host copy of the batch
+  Segment sg;
+  sg.in = in;
+  sg.in.h_data = nullptr;
+  sg.bytes = total;
+  if (before_confirm && *before_confirm) (*before_confirm)();    // (the caller's batch may be gone from here on)
+  results->clear();
+  results->resize(nfiles);
+  uint64_t nconf = 0, nfind = 0;
+  CallCtx* cc = acquire_call();
+  try {
+    confirm_segment(*cc, sg, g, results->data(), &nconf, &nfind, false);
+  } catch (const std::exception& x) {
+    release_call(cc);
+    *err = x.what();
+    return false;
+  }
+  release_call(cc);
+  if (st) {
+    *st = ScanStats();
+    st->bytes = total;
+    st->files = nfiles;
+    st->confirm_files = nconf;
+    st->findings = nfind;
+    st->chunk_bytes = chunk;
+    st->gather_files = g.gather_files;
+    st->gather_bytes = gp.total;
+    st->gather_runs = gp.runs.size();
+  }
+  if (raw) {
+    *raw = RawScan();
+    raw->segs.resize(1);
+    RawSegment& rec = raw->segs[0];
+    rec.nfiles = nfiles;
+    rec.bytes = total;
+    rec.chunk = chunk;
+    rec.need = need;
+    rec.goff = gp.goff;
+    rec.runs = gp.runs;
+    rec.gather_total = gp.total;
+    rec.gathered = buf;
+  }
+  return true;
+}
+
 void Engine::release_call(CallCtx* cc) {
   std::lock_guard<std::mutex> lk(call_mu_);
   free_calls_.push_back(cc);
@@ -2128,6 +2321,9 @@ struct SegRun {
   uint32_t* k2_trace = nullptr;
   double t_sync = 0;                          // host wall time from t0 to the results
   float k1_ms = 0, k2_ms = 0;
+  // device-only scans: gather the confirmer's files behind K2 (lead: files never gathered)
+  bool gather = false, keep_gather = false;
+  uint32_t lead = 0;
 };
 
 namespace {
@@ -2221,7 +2417,9 @@ bool Engine::seg_size_scratch(SegRun& r, std::string* err) {
          ln.d_ff.ensure(std::max<uint32_t>(in.nfiles, 1), err) &&
          // deferred-output slots: kOutSlots per thread (x2 grid slack)
          ln.d_ob.ensure(static_cast<size_t>(sms) * 1024 * 2 * kOutSlots, err) &&
-         (!file_index_ || !r.nfidx || ln.d_fidx.ensure(r.nfidx, err));
+         (!file_index_ || !r.nfidx || ln.d_fidx.ensure(r.nfidx, err)) &&
+         (!r.gather || (ln.d_need.ensure(in.nfiles, err) && ln.d_goff.ensure(in.nfiles, err) &&
+                        ln.d_gruns.ensure((static_cast<size_t>(in.nfiles) + 1) / 2 + 1, err) && ln.d_gmeta.ensure(2, err)));
 }
 
 // K1's grid for this attempt, and the prologue: keyword bits, file flags,
@@ -2412,6 +2610,38 @@ bool Engine::seg_readback_wait(SegRun& r, int a2, std::string* err) {
   rb.add(ln.d_nl.p, ln.rb_nl, (r.nchunks + 1) / 2);
   rb.add(ln.d_cands.p, ln.rb_cands, ln.cand_cap * (sizeof(CandDev) / 4), ln.d_cnt.p + 1, sizeof(CandDev) / 4);
   if (!rb.launch(s, err)) return false;
+  if (r.gather) {
+    // the gather's layout rides the same round trip (a launch of its own:
+    // tsg_readback's region list is full); need and the run table only for
+    // tsg_test_keep_gather
+    if (!ln.rb_gmeta.ensure_readback(16, err) || !ln.rb_goff.ensure_readback(nfiles * sizeof(uint64_t), err)) return false;
+    Readbacks rg;
+    rg.add(ln.d_gmeta.p, ln.rb_gmeta, 4);
+    rg.add(ln.d_goff.p, ln.rb_goff, 2ull * nfiles);
+    if (r.keep_gather) {
+      const size_t max_runs = (static_cast<size_t>(nfiles) + 1) / 2 + 1;
+      if (!ln.rb_need.ensure_readback(nfiles, err) || !ln.rb_gruns.ensure_readback(max_runs * sizeof(GatherRun), err))
+        return false;
+      rg.add(ln.d_need.p, ln.rb_need, (nfiles + 3) / 4);
+      rg.add(ln.d_gruns.p, ln.rb_gruns, max_runs * (sizeof(GatherRun) / 4),
+             reinterpret_cast<const uint32_t*>(ln.d_gmeta.p), sizeof(GatherRun) / 4);
+    }
+    if (!rg.launch(s, err)) return false;
+  }
+  if (!seg_wait(r, err)) return false;
+  r.t_sync = ms_since(r.t0);
+  if (ln.rb_c2.as<const uint32_t>()[3] != 0) { *err = "K1: dynamic LDS does not start at address 0"; return false; }
+  HIP_OK(hipEventElapsedTime(&r.k1_ms, ln.ev[0], ln.ev[1]));
+  HIP_OK(hipEventElapsedTime(&r.k2_ms, a2 > 0 ? ln.ev[2] : ln.ev[1], ln.ev[3]));
+  if (a2 == 0) r.st->k1_ms += r.k1_ms;
+  r.st->k2_ms += r.k2_ms;
+  return true;
+}
+
+// The driver waits for everything queued on the segment's compute stream.
+bool Engine::seg_wait(SegRun& r, std::string* err) {
+  Lane& ln = r.ln;
+  hipStream_t s = ln.compute;
   if (r.chain) {
     // polled with short sleeps: a blocking-sync event woke its driver
     // 0.3-1.2 ms after the passes ended (profiles/rd5e_bench_c2prof.log)
@@ -2434,12 +2664,85 @@ bool Engine::seg_readback_wait(SegRun& r, int a2, std::string* err) {
     // profiles/r5i_small.log; the stream synchronization stays)
     HIP_OK(hipStreamSynchronize(s));
   }
-  r.t_sync = ms_since(r.t0);
-  if (ln.rb_c2.as<const uint32_t>()[3] != 0) { *err = "K1: dynamic LDS does not start at address 0"; return false; }
-  HIP_OK(hipEventElapsedTime(&r.k1_ms, ln.ev[0], ln.ev[1]));
-  HIP_OK(hipEventElapsedTime(&r.k2_ms, a2 > 0 ? ln.ev[2] : ln.ev[1], ln.ev[3]));
-  if (a2 == 0) r.st->k1_ms += r.k1_ms;
-  r.st->k2_ms += r.k2_ms;
+  return true;
+}
+
+// Device-only scans: behind the segment's K2 (inside the candidate-overflow
+// retry loop, so the last launch saw the final list) the GPU marks the files
+// the confirmer will read, lays their runs out and stores them into the
+// segment's gather buffer; the layout comes back with the other readbacks.
+bool Engine::seg_launch_gather(SegRun& r, GpuOut* out, std::string* err) {
+  Lane& ln = r.ln;
+  hipStream_t s = ln.compute;
+  if (!out->gather.b) {
+    const size_t first = gather_cap_ ? gather_cap_ : r.total / 8 + (1u << 20);
+    if (!out->gather.take(r.dt, std::max(first, ln.gather_cap), err)) return false;
+    out->gbase = out->gather.host();
+    if (r.keep_gather) std::memset(out->gather.host() + out->gather.cap(), 0xA5, kGatherGuard);
+  }
+  for (auto& e : ln.gev) if (!e) HIP_OK(hipEventCreate(&e));
+  bool all = false;
+  for (const auto& pr : pf_.rules) all = all || pr.mode == 1;
+  HIP_OK(hipEventRecord(ln.gev[0], s));
+  if (!gather_plan_launch(ln.d_cands.p, ln.d_cnt.p + 1, static_cast<uint32_t>(ln.cand_cap), ln.d_ff.p, r.d_off,
+                          r.in.nfiles, r.lead, all, r.chunk, ln.d_need.p, ln.d_goff.p, ln.d_gruns.p, ln.d_gmeta.p, s, err) ||
+      !gather_copy_launch(r.d_data, ln.d_gruns.p, ln.d_gmeta.p, static_cast<uint8_t*>(out->gather.b->mem.d),
+                          out->gather.cap(), static_cast<uint32_t>(std::max(r.dt.sms, 1)) * 8u, s, err))
+    return false;
+  HIP_OK(hipEventRecord(ln.gev[1], s));
+  return true;
+}
+
+// The readback is in: the gather's totals into the stats and, while the runs
+// did not fit the buffer (the copy then wrote nothing), a larger buffer and
+// the copy alone again -- the layout on the device is still this segment's.
+bool Engine::seg_gather_retry(SegRun& r, GpuOut* out, std::string* err) {
+  Lane& ln = r.ln;
+  const uint64_t* meta = ln.rb_gmeta.as<const uint64_t>();
+  const uint64_t nruns = meta[0], total = meta[1];
+  auto note = [&] {                                  // tsg_test_keep_gather: this launch's capacity and its guard
+    if (!r.keep_gather) return;
+    const uint8_t* gp = out->gather.host() + out->gather.cap();
+    bool whole = true;
+    for (size_t k = 0; k < kGatherGuard; ++k) whole = whole && gp[k] == 0xA5;
+    out->gather_caps.push_back(out->gather.cap());
+    out->guard_ok.push_back(whole ? 1 : 0);
+  };
+  float ms = 0;
+  HIP_OK(hipEventElapsedTime(&ms, ln.gev[0], ln.gev[1]));
+  note();
+  for (int k = 0; total > out->gather.cap(); ++k) {
+    if (k == 3) { *err = "gather buffer overflow persisted"; return false; }
+    const size_t want = static_cast<size_t>(gather_round(total + total / 4));
+    if (!out->gather.take(r.dt, want, err)) return false;
+    out->gbase = out->gather.host();
+    if (r.keep_gather) std::memset(out->gather.host() + out->gather.cap(), 0xA5, kGatherGuard);
+    HIP_OK(hipEventRecord(ln.gev[0], ln.compute));
+    if (!gather_copy_launch(r.d_data, ln.d_gruns.p, ln.d_gmeta.p, static_cast<uint8_t*>(out->gather.b->mem.d),
+                            out->gather.cap(), static_cast<uint32_t>(std::max(r.dt.sms, 1)) * 8u, ln.compute, err))
+      return false;
+    HIP_OK(hipEventRecord(ln.gev[1], ln.compute));
+    if (!seg_wait(r, err)) return false;
+    float ms2 = 0;
+    HIP_OK(hipEventElapsedTime(&ms2, ln.gev[0], ln.gev[1]));
+    ms += ms2;
+    note();
+    ++r.st->gather_retries;
+  }
+  ln.gather_cap = std::max(ln.gather_cap, out->gather.cap());
+  out->gathered = true;
+  out->gather_total = total;
+  out->rb_goff = ln.rb_goff.as<uint64_t>();
+  out->n_goff = r.in.nfiles;
+  if (r.keep_gather) {
+    out->rb_need = ln.rb_need.as<uint8_t>();
+    out->n_need = r.in.nfiles;
+    out->rb_gruns = ln.rb_gruns.as<GatherRun>();
+    out->n_gruns = static_cast<size_t>(nruns);
+  }
+  r.st->gather_bytes += total;
+  r.st->gather_runs += nruns;
+  r.st->gather_ms += ms;
   return true;
 }
 
@@ -2517,8 +2820,19 @@ bool Engine::fold_k2_stats(Lane& ln, std::string* err) {
 // seen afterwards, grown, and the pass run again.
 bool Engine::run_segment(DeviceTables& dt, Lane& ln, const Segment& sg, const void* d_data, const uint64_t* d_off_up,
                          ScanStats* st, GpuOut* out, std::string* err, const std::function<void()>* while_gpu,
-                         K1Chain* chain, bool defer_copy, const StageIn* stage_in) {
+                         K1Chain* chain, bool defer_copy, const StageIn* stage_in, bool gather) {
   SegRun r{dt, ln, sg.in, st, chain};
+  // device-only scans: a failed call gives its gather buffer back to the pool
+  // with `out`, which another scan may take (or free to grow it) at once, so
+  // nothing queued here may still be storing into it when this returns false
+  struct DrainOnFailure {
+    hipStream_t s;
+    bool armed;
+    ~DrainOnFailure() { if (armed) (void)hipStreamSynchronize(s); }
+  } drain{ln.compute, gather};
+  r.gather = gather;
+  r.keep_gather = gather && keep_gather();
+  r.lead = sg.lead;
   r.d_data = static_cast<const uint8_t*>(d_data);
   r.d_off = const_cast<uint64_t*>(d_off_up);
   if (stage_in) r.stage = *stage_in;
@@ -2537,6 +2851,7 @@ bool Engine::run_segment(DeviceTables& dt, Lane& ln, const Segment& sg, const vo
     bool rerun_k1 = false;
     for (int a2 = 0; a2 < 3 && !rerun_k1; ++a2) {
       if (!seg_launch_k2(r, a2, err)) return false;
+      if (r.gather && !seg_launch_gather(r, out, err)) return false;
       // (before this segment's readbacks are queued: the callback may copy
       // the lane's previous segment out of the readback buffers)
       if (while_gpu && *while_gpu) {
@@ -2556,11 +2871,14 @@ bool Engine::run_segment(DeviceTables& dt, Lane& ln, const Segment& sg, const vo
         break;
       }
       if (ncands > ln.cand_cap) { ln.cand_cap = static_cast<size_t>(ncands) * 5 / 4 + 1024; continue; }
+      if (r.gather && !seg_gather_retry(r, out, err)) return false;
       seg_hand_off(r, ncands, nover, defer_copy, out);
 #ifdef TSG_K1_PROBE
       if (!seg_write_traces(r, err)) return false;
 #endif
-      return !ln.d_k2s.p || fold_k2_stats(ln, err);
+      const bool ok = !ln.d_k2s.p || fold_k2_stats(ln, err);
+      drain.armed = !ok && gather;
+      return ok;
     }
     if (rerun_k1) continue;
     *err = "candidate buffer overflow persisted";
@@ -2581,9 +2899,26 @@ bool Engine::prefilter_only(const BatchInput& in, std::vector<std::vector<std::v
   Segment sg;
   sg.in = in;
   GpuOut out;
-  const bool ok = run_segment(dt, *ln, sg, in.d_data, nullptr, st, &out, err);
+  // tsg_test_keep_gather and no host copy: the device-only scan's gather runs
+  // behind K2 as in scan(), and its record comes back with the raw outputs
+  const bool gather = raw && !in.h_data && keep_gather();
+  const bool ok = run_segment(dt, *ln, sg, in.d_data, nullptr, st, &out, err, nullptr, nullptr, false, nullptr, gather);
   release_lane(dt, ln);
   if (!ok) return false;
+  if (gather) {
+    RawSegment& rec = raw->gather;
+    rec.nfiles = in.nfiles;
+    rec.bytes = in.offsets[in.nfiles];
+    rec.chunk = out.chunk;
+    rec.need = out.need;
+    rec.goff = out.goff;
+    rec.runs = out.gruns;
+    rec.gather_total = out.gather_total;
+    rec.gather_caps = out.gather_caps;
+    rec.guard_ok = out.guard_ok;
+    rec.gathered.assign(out.gbase, out.gbase + out.gather_total);
+    for (uint64_t o : out.goff) st->gather_files += o != kGatherNone;
+  }
   const size_t nr = pf_.rules.size();   // the rules, then the exclude-block pseudo-rules
   if (cands) {
     cands->assign(in.nfiles, std::vector<std::vector<uint64_t>>(nr));
@@ -3069,6 +3404,38 @@ void Engine::plan_confirm(const Segment& sg, GpuOut* gp) const {
   g.planned = true;
 }
 
+namespace {
+
+// Where the confirmer reads a segment's bytes -- the only reader of
+// BatchInput::h_data on the confirm path: the caller's host copy
+// (std::false_type), or a device-only scan's gather buffer through the
+// device's goff (std::true_type).  The confirm worker is instantiated once per
+// source, so neither pays a branch per file for the other.
+struct ConfirmBytes {
+  const uint8_t* h;
+  const uint64_t* off;
+  const uint8_t* gbuf;
+  const uint64_t* goff;
+  const uint8_t* content(std::false_type, uint32_t f) const { return h + off[f]; }
+  const uint8_t* content(std::true_type, uint32_t f) const { return gbuf + goff[f]; }
+  // K1's newline counts are per chunk of the segment's frame; prefix_at also
+  // reads the bytes between the chunk boundary below the file and the file
+  void newlines(std::false_type, uint32_t f, uint32_t, NlSource* n) const {
+    n->data = h;
+    n->file_off = off[f];
+  }
+  // (the gather starts every run on that boundary, so the head bytes are in
+  // the buffer in front of the file: no pointer outside it is formed)
+  void newlines(std::true_type, uint32_t f, uint32_t chunk, NlSource* n) const {
+    const uint64_t head = off[f] % chunk;
+    n->data = gbuf + (goff[f] - head);
+    n->data_off = off[f] - head;
+    n->file_off = off[f];
+  }
+};
+
+}  // namespace
+
 void Engine::confirm_segment(CallCtx& cc, const Segment& sg, GpuOut& g, Secret* results, uint64_t* nconf_out,
                              uint64_t* nfind_out, bool gpu_in_flight) {
   const BatchInput& in = sg.in;
@@ -3076,6 +3443,22 @@ void Engine::confirm_segment(CallCtx& cc, const Segment& sg, GpuOut& g, Secret* 
   const size_t nplan = pf_.rules.size();   // rules + exclude-block pseudo-rules
   const auto t_begin = std::chrono::steady_clock::now();
   if (!g.planned) plan_confirm(sg, &g);
+  const ConfirmBytes src{in.h_data, in.offsets, g.gbase, g.goff.data()};
+  if (g.gathered) {
+    // a file to confirm that the device did not gather (or placed outside
+    // what it gathered) fails the call: it is never scanned from wrong bytes
+    if (g.goff.size() != in.nfiles || (!g.gbase && g.gather_total)) throw std::runtime_error("device-only scan: no gather for the segment");
+    for (uint32_t f : g.work) {
+      const uint64_t o = g.goff[f], head = in.offsets[f] % g.chunk;
+      if (o == kGatherNone || o < head || o > g.gather_total || in.offsets[f + 1] - in.offsets[f] > g.gather_total - o)
+        throw std::runtime_error("device-only scan: a file the confirmer reads was not gathered");
+    }
+    uint64_t nf = 0;
+    for (uint32_t f = sg.lead; f < in.nfiles; ++f) nf += g.goff[f] != kGatherNone;
+    g.gather_files = nf;
+  } else if (!in.h_data && !g.work.empty()) {
+    throw std::runtime_error("scan without a host copy of the batch and without a gather");
+  }
   const std::vector<uint32_t>& per_file = g.per_file;
   std::vector<CandDev>& sorted = g.sorted;
   const std::vector<uint32_t>& work = g.work;
@@ -3114,7 +3497,7 @@ void Engine::confirm_segment(CallCtx& cc, const Segment& sg, GpuOut& g, Secret* 
       }
     }
   };
-  auto worker = [&]() {
+  auto worker = [&](auto from) {               // from: where the bytes are (ConfirmBytes)
     FilePlan plan;
     std::vector<std::vector<uint64_t>> spare;
     // per-thread counts and work taken a few files at a time: 15 threads
@@ -3138,7 +3521,7 @@ void Engine::confirm_segment(CallCtx& cc, const Segment& sg, GpuOut& g, Secret* 
         const uint32_t fn = work[wi];
         __builtin_prefetch(results + fn, 1);
         __builtin_prefetch(in.paths[fn]);
-        const uint8_t* cn = in.h_data + in.offsets[fn];
+        const uint8_t* cn = src.content(from, fn);
         const uint64_t ln = in.offsets[fn + 1] - in.offsets[fn];
         for (uint32_t k = per_file[fn], ke = std::min(per_file[fn + 1], per_file[fn] + 4); k < ke; ++k) {
           const uint64_t st = sorted[k].start;
@@ -3151,7 +3534,7 @@ void Engine::confirm_segment(CallCtx& cc, const Segment& sg, GpuOut& g, Secret* 
       const auto tp0 = prof ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
       const char* path_p = in.paths[f];
       const size_t path_n = in.path_lens ? in.path_lens[f] : std::strlen(path_p);
-      const uint8_t* content = in.h_data + in.offsets[f];
+      const uint8_t* content = src.content(from, f);
       const size_t len = in.offsets[f + 1] - in.offsets[f];
       const bool binary = in.binary ? in.binary[f] != 0 : false;
       const uint32_t cb = per_file[f], ce = per_file[f + 1];
@@ -3210,8 +3593,7 @@ void Engine::confirm_segment(CallCtx& cc, const Segment& sg, GpuOut& g, Secret* 
       }
       NlSource nls;
       nls.chunk_nl = g.nl.data();
-      nls.data = in.h_data;
-      nls.file_off = in.offsets[f];
+      src.newlines(from, f, g.chunk, &nls);
       nls.chunk = g.chunk;
       const auto tp1 = prof ? std::chrono::steady_clock::now() : tp0;
       Secret s = scan_file(rs, path_p, path_n, content, len, binary, &plan, &nls);
@@ -3245,7 +3627,8 @@ void Engine::confirm_segment(CallCtx& cc, const Segment& sg, GpuOut& g, Secret* 
   auto body = [&](int idx) {
     if (idx >= active) return;
     auto a = std::chrono::steady_clock::now();
-    worker();
+    if (g.gathered) worker(std::true_type());
+    else worker(std::false_type());
     auto b = std::chrono::steady_clock::now();
     light_files();
     work_us.fetch_add(std::chrono::duration_cast<std::chrono::microseconds>(b - a).count());
@@ -3305,6 +3688,15 @@ void record_raw_segment(const Segment& sg, const ScanJob& job, size_t nrules, Ra
   std::sort(lead.begin(), lead.end());
   lead.erase(std::unique(lead.begin(), lead.end()), lead.end());
   for (const auto& c : lead) { rec.lead_rules.push_back(c.first); rec.lead_starts.push_back(c.second); }
+  if (g.gathered && !g.gather_caps.empty()) {       // tsg_test_keep_gather
+    rec.need = g.need;
+    rec.goff = g.goff;
+    rec.runs = g.gruns;
+    rec.gather_total = g.gather_total;
+    rec.gather_caps = g.gather_caps;
+    rec.guard_ok = g.guard_ok;
+    rec.gathered.assign(g.gbase, g.gbase + g.gather_total);
+  }
 }
 
 }  // namespace
@@ -3321,6 +3713,7 @@ struct ScanCall {
   ScanStats* st;
   bool resident = false;
   bool dual = false;                   // resident batches of several pieces: two drivers on the device (K1Chain)
+  bool device_only = false;            // resident without a host copy: the GPU gathers the confirmer's files
   K1Chain chain;
   const uint8_t* h_dev = nullptr;      // a direct batch: the device view of its pinned bytes
   bool wire_want = false;
@@ -3423,7 +3816,8 @@ struct SegmentDriver {
     const double h_start = ms_since(sc.t_feed0);
     if (!eng.run_segment(*dt, *ln, sg, resident ? sg.in.d_data : ln->ring[slot].p,
                          resident ? nullptr : ln->off_slot[slot].p, &sst, &job->out, &e, &plan_fn,
-                         sc.dual ? &sc.chain : nullptr, /*defer_copy=*/true, direct ? &stage : nullptr))
+                         sc.dual ? &sc.chain : nullptr, /*defer_copy=*/true, direct ? &stage : nullptr,
+                         /*gather=*/sc.device_only))
       return false;
     if (wf) wf->segment_done();        // this segment's ring slot may be written again
     else if (!resident) sst.wire_bytes += sg.bytes;
@@ -3584,6 +3978,7 @@ bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::
   ScanCall sc{*this, segs, drivers, pipe, st};
   sc.resident = resident;
   sc.dual = dual;
+  sc.device_only = resident && !in.h_data;
   for (const Segment& sg : segs) {
     sc.max_seg = std::max(sc.max_seg, sg.bytes);
     sc.max_seg_files = std::max<size_t>(sc.max_seg_files, sg.in.nfiles);
@@ -3598,7 +3993,7 @@ bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::
   sc.wire_want = wire_mode_ != 0 && !resident && !sc.direct() && in.h_data && drivers.size() == 1 &&
                  total >= 4 * wire_strip_ && !dense_batch(in.nfiles, total, seg_);
   CallCtx* cc = acquire_call();
-  uint64_t nconf = 0, nfind = 0;
+  uint64_t nconf = 0, nfind = 0, ngather = 0;
   double host_ms = 0;
   // one segment on one device (per-file Scan batches, small batches): the
   // driver runs on this thread -- a thread start and hand-off cost more than
@@ -3623,6 +4018,7 @@ bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::
         if (raw) record_raw_segment(sg, job, pf_.rules.size(), raw);
         // (drivers that block on an event leave every core to the pool)
         confirm_segment(*cc, sg, job.out, results->data() + sg.f0, &nconf, &nfind, left > 0 && !dual);
+        ngather += job.out.gather_files;
         sc.confirmer_idle.store(true, std::memory_order_release);
         host_ms += ms_since(th);
         if (host_profile_) std::fprintf(stderr, "[tsg tl] seg %zu confirm %.3f-%.3f ms\n", job.seg, c_start, ms_since(sc.t_feed0));
@@ -3643,6 +4039,7 @@ bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::
   st->host_ms = host_ms;
   st->confirm_files = nconf;
   st->findings = nfind;
+  st->gather_files = ngather;
   st->feed_ms = resident ? 0.0 : sc.feed_end_ns.load() / 1e6;
   st->total_ms = ms_since(t0);
   return true;

@@ -596,6 +596,7 @@ class CensoredView {
       // local prefix over the batch chunks this file touches
       ch_ = nl->chunk;
       data_ = nl->data;
+      data_off_ = nl->data_off;
       off_ = nl->file_off;
       first_ = off_ / ch_;
       // prefix_at(g) reads local_[g / ch_ - first_] for g <= off_ + n: only
@@ -685,6 +686,7 @@ class CensoredView {
   const uint16_t* chunk_nl_ = nullptr;      // per-chunk counts (K1's), summed into local_ on demand
   const uint8_t* data_ = nullptr;
   uint64_t off_ = 0, first_ = 0;
+  uint64_t data_off_ = 0;                   // data_[0] is byte data_off_ of the batch (<= first_ * ch_)
   uint32_t ch_ = 4096;
 
   // the merged spans are sorted and disjoint: the first one ending after a
@@ -699,7 +701,7 @@ class CensoredView {
         local_.push_back(local_.back() + chunk_nl_[j]);
       }
     }
-    return local_[k - first_] + count_newlines(data_ + k * ch_, g - k * ch_);
+    return local_[k - first_] + count_newlines(data_ + (k * ch_ - data_off_), g - k * ch_);
   }
   uint64_t orig_nl(size_t a, size_t b) const {
     if (b - a <= 2 * static_cast<size_t>(ch_)) return count_newlines(c_ + a, b - a);

@@ -254,8 +254,12 @@ struct FilePlan {
 // '\n' counts over the packed batch (chunk c covers data[c*chunk, (c+1)*chunk)).
 struct NlSource {
   const uint16_t* chunk_nl = nullptr;
-  const uint8_t* data = nullptr;      // packed batch (host)
-  uint64_t file_off = 0;              // global offset of this file in data
+  const uint8_t* data = nullptr;      // packed batch (host), from its byte data_off on
+  // byte of the batch data[0] is (a chunk boundary at or below the file's
+  // first chunk); 0: data is the whole batch.  A device-only scan's gather
+  // buffer holds a file from the chunk boundary below it only.
+  uint64_t data_off = 0;
+  uint64_t file_off = 0;              // global offset of this file in the batch
   uint32_t chunk = 0;
 };
 

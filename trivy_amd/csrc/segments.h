@@ -11,7 +11,8 @@
 namespace tsg {
 
 struct BatchInput {
-  const uint8_t* h_data = nullptr;     // host copy (needed by the exact confirmer)
+  const uint8_t* h_data = nullptr;     // host copy for the exact confirmer; nullptr with d_data set: a
+                                       // device-only scan (the confirmer reads the GPU's gather of the batch)
   const void* d_data = nullptr;        // device copy; nullptr -> engine uploads h_data
   const uint64_t* offsets = nullptr;   // nfiles + 1 byte offsets into data
   uint32_t nfiles = 0;
@@ -160,13 +161,13 @@ inline void plan_segments(const BatchInput& in, bool resident, const SegmentPoli
     // (aligned pieces 1.5, profiles/rd4k traffic runs).  Start it at the
     // 256-byte boundary below, the bytes in between a lead file.
     const uint64_t delta = resident && k > 0 ? (reinterpret_cast<uintptr_t>(in.d_data) + sg.b0) & 255u : 0;
-    if (delta && in.h_data && in.paths) {
+    if (delta && in.paths) {               // (h_data is null in a device-only scan)
       sg.lead = 1;
       sg.off.insert(sg.off.begin(), 0);
       for (size_t i = 1; i < sg.off.size(); ++i) sg.off[i] += delta;
       q.offsets = sg.off.data();
       q.nfiles = b - a + 1;
-      q.h_data -= delta;
+      if (q.h_data) q.h_data -= delta;
       q.d_data = static_cast<const uint8_t*>(q.d_data) - delta;
       sg.lead_paths.assign(1, "");
       sg.lead_paths.insert(sg.lead_paths.end(), in.paths + a, in.paths + b);

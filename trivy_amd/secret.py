@@ -205,6 +205,71 @@ class Scanner:
             s.pop("Error", None)
         return (out, stats) if with_stats else out
 
+    def _scan_device_tensor(self, d_data, offsets, paths, binary, h_data, with_stats):
+        """tsg_scan_batch_device (h_data None) or tsg_scan_batch_resident on a
+        uint8 device tensor; returns (findings, stats or None, C result)."""
+        import torch
+        L = _lib.lib()
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        nfiles = len(off) - 1
+        if nfiles != len(paths):
+            raise ValueError("offsets must hold one more entry than paths")
+        total = int(off[-1]) if nfiles else 0
+        if d_data.dtype != torch.uint8 or not d_data.is_cuda or not d_data.is_contiguous():
+            raise ValueError("d_data must be a contiguous uint8 device tensor")
+        if d_data.numel() < total + 16 or d_data.data_ptr() % 16:
+            raise ValueError("d_data must be 16-byte aligned and hold 16 bytes past the batch")
+        cpaths, lens, _keep = _lib.pack_paths(paths)
+        b = np.ascontiguousarray(binary if binary is not None else np.zeros(max(nfiles, 1)), dtype=np.uint8)
+        torch.cuda.current_stream(d_data.device).synchronize()     # the engine runs on its own streams
+        res = ctypes.c_void_p()
+        if h_data is None:
+            _lib.check(L.tsg_scan_batch_device(self.engine(), ctypes.c_void_p(d_data.data_ptr()), off.ctypes.data,
+                                               nfiles, cpaths, lens, b.ctypes.data, ctypes.byref(res)))
+        else:
+            h = np.ascontiguousarray(h_data, dtype=np.uint8)
+            if len(h) < total:
+                raise ValueError("h_data is shorter than the batch")
+            _lib.check(L.tsg_scan_batch_resident(self.engine(), ctypes.c_void_p(d_data.data_ptr()), h.ctypes.data,
+                                                 off.ctypes.data, nfiles, cpaths, lens, b.ctypes.data,
+                                                 ctypes.byref(res)))
+        try:
+            out = _lib.result_json(res)
+            stats = None
+            if with_stats:
+                stats = _lib.result_stats(res)
+                stats.update(_lib.result_gather_stats(res))
+        finally:
+            L.tsg_result_free(res)
+        for s in out:
+            s.pop("Error", None)
+        return (out, stats) if with_stats else out
+
+    def ScanBatchDevice(self, d_data, offsets, paths, binary=None, with_stats=False):
+        """The device-only scan (tsg_scan_batch_device): the batch exists only
+        in HBM.  d_data: uint8 device tensor, the files packed back to back,
+        16-byte aligned, with at least 16 bytes after the batch; offsets:
+        nfiles + 1 host integers (0 ... total); paths: the files' FilePath;
+        binary: optional per-file flags.  After its second pass the GPU
+        gathers the files the exact confirmer reads into host memory; nothing
+        else of the batch crosses the link.  The caller's stream is
+        synchronised first.  with_stats adds the scan's stats and the gather's
+        (gather_files, gather_bytes, gather_runs, gather_ms, gather_retries).
+
+        The chain for files uploaded as read, CRLF line ends included:
+
+            dst, new_off, total, _ = sc.StripCR(d_raw, d_raw_offsets, nfiles, raw_total)
+            found = sc.ScanBatchDevice(dst, new_off.cpu().numpy(), paths)
+
+        -- the stripped bytes stay on the device; only the offsets come back."""
+        return self._scan_device_tensor(d_data, offsets, paths, binary, None, with_stats)
+
+    def ScanBatchResident(self, d_data, h_data, offsets, paths, binary=None, with_stats=False):
+        """tsg_scan_batch_resident: as ScanBatchDevice, with the caller's host
+        copy h_data (uint8 array of the batch) for the confirmer instead of
+        the GPU's gather."""
+        return self._scan_device_tensor(d_data, offsets, paths, binary, h_data, with_stats)
+
 
 NewScanner = Scanner
 
@@ -761,6 +826,144 @@ def scan_raw(scanner, args_list, resident=False, base=0, pinned=True, data_shift
         if pin:
             L.tsg_free_pinned(pin)
         del d
+
+
+def plan_gather(offsets, need, chunk, lead=0):
+    """The device-only scan's gather layout (tsg_test_plan_gather, csrc/gather.h):
+    (goff np.uint64 per file, runs np.uint64 [nruns, 3] of (source, destination,
+    length), total).  Tests only."""
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    nd = np.ascontiguousarray(need, dtype=np.uint8)
+    nfiles = len(off) - 1
+    goff = np.zeros(max(nfiles, 1), np.uint64)
+    runs = np.zeros((nfiles // 2 + 2, 3), np.uint64)
+    nruns, total = ctypes.c_size_t(), ctypes.c_uint64()
+    _lib.check(_lib.lib().tsg_test_plan_gather(off.ctypes.data, nfiles, lead, nd.ctypes.data, chunk, goff.ctypes.data,
+                                                runs.ctypes.data, len(runs), ctypes.byref(nruns),
+                                                ctypes.byref(total)))
+    return goff[:nfiles], runs[:nruns.value].copy(), total.value
+
+
+def _gather_segment(res, k):
+    """Segment k's gather record of a result (tsg_result_gather_segment) as a dict."""
+    rec = _lib.TsgGatherSegment()
+    _lib.check(_lib.lib().tsg_result_gather_segment(res, k, ctypes.byref(rec)))
+
+    def arr(p, ctype, dtype, count):
+        if not count:
+            return np.zeros(0, dtype)
+        return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctype)), shape=(count,)).copy()
+    return {"nfiles": rec.nfiles, "total": rec.total,
+            "need": arr(rec.need, ctypes.c_uint8, np.uint8, rec.nfiles if rec.need else 0),
+            "goff": arr(rec.goff, ctypes.c_uint64, np.uint64, rec.nfiles),
+            "runs": arr(rec.runs, ctypes.c_uint64, np.uint64, 3 * rec.nruns).reshape(-1, 3),
+            "caps": arr(rec.caps, ctypes.c_uint64, np.uint64, rec.ncaps).tolist(),
+            "guard_ok": arr(rec.guard_ok, ctypes.c_uint8, np.uint8, rec.ncaps).tolist(),
+            "bytes": arr(rec.bytes, ctypes.c_uint8, np.uint8, rec.total)}
+
+
+def scan_device_model(scanner, args_list, chunk, with_gather=False):
+    """CPU model of the device-only scan (tsg_scan_device_model): findings, and
+    with_gather the gather record and stats.  Tests only."""
+    data, offsets = pack(args_list)
+    paths, lens, _keep = _lib.pack_paths([a.FilePath for a in args_list])
+    binary = np.array([1 if a.Binary else 0 for a in args_list] or [0], dtype=np.uint8)
+    res = ctypes.c_void_p()
+    _lib.check(_lib.lib().tsg_scan_device_model(scanner._rs, data.ctypes.data, offsets.ctypes.data, len(args_list),
+                                                paths, lens, binary.ctypes.data, chunk, ctypes.byref(res)))
+    try:
+        out = _lib.result_json(res)
+        for s in out:
+            s.pop("Error", None)
+        if not with_gather:
+            return out
+        return out, _gather_segment(res, 0), _lib.result_gather_stats(res)
+    finally:
+        _lib.lib().tsg_result_free(res)
+
+
+def scan_device_raw(scanner, args_list, base=0, pad=16, tail=None, device="cuda:0"):
+    """tsg_scan_batch_device with the raw-output and keep-gather hooks on (they
+    stay on for the scanner's engine).  The batch lies `base` bytes (a multiple
+    of 16) above a 256-byte boundary of a device tensor that ends `pad` bytes
+    after the batch; no host array of the batch is passed to the call.
+    Returns (findings, {(file, rule): starts}, info) as scan_raw, each
+    info["segments"][k] also holding "gather" (_gather_segment), and
+    info["gather_stats"].  Tests only."""
+    import torch
+    L = _lib.lib()
+    data, offsets = pack(args_list)
+    total = int(offsets[-1])
+    paths, lens, _keep = _lib.pack_paths([a.FilePath for a in args_list])
+    binary = np.array([1 if a.Binary else 0 for a in args_list] or [0], dtype=np.uint8)
+    eng = scanner.engine()
+    _lib.check(L.tsg_test_keep_raw(eng, 1))
+    _lib.check(L.tsg_test_keep_gather(eng, 1))
+    full = torch.zeros(base + total + pad, dtype=torch.uint8, device=device)
+    if full.data_ptr() % 256 != 0 or base % 16 != 0 or pad < 16:
+        raise ValueError("scan_device_raw: device allocation, base or pad is not as required")
+    host = data[:total + pad].copy()
+    if tail is not None:
+        host[total:] = np.frombuffer((tail * pad)[:pad], dtype=np.uint8)
+    full[base:].copy_(torch.from_numpy(host))
+    torch.cuda.synchronize()
+    res = ctypes.c_void_p()
+    try:
+        _lib.check(L.tsg_scan_batch_device(eng, ctypes.c_void_p(full.data_ptr() + base), offsets.ctypes.data,
+                                           len(args_list), paths, lens, binary.ctypes.data, ctypes.byref(res)))
+        findings = _lib.result_json(res)
+        for s in findings:
+            s.pop("Error", None)
+        ns = ctypes.c_size_t()
+        _lib.check(L.tsg_result_raw_segments(res, ctypes.byref(ns)))
+        segs = []
+        for k in range(ns.value):
+            rec = _lib.TsgRawSegment()
+            _lib.check(L.tsg_result_raw_segment(res, k, ctypes.byref(rec)))
+            sd = {f: getattr(rec, f) for f in ("f0", "nfiles", "lead", "chunk_bytes", "b0", "bytes", "lead_bytes")}
+            sd["gather"] = _gather_segment(res, k)
+            segs.append(sd)
+        info = {"flags": _result_file_flags(res), "segments": segs, "stats": _lib.result_stats(res),
+                "gather_stats": _lib.result_gather_stats(res)}
+        return findings, _result_candidates(res), info
+    finally:
+        if res:
+            L.tsg_result_free(res)
+        del full
+
+
+def prefilter_device_gather(scanner, args_list, device="cuda:0"):
+    """The two GPU passes and the device-only scan's gather on one resident
+    segment, without a confirmation (tsg_prefilter_resident with h_data NULL and
+    the keep-gather hook on): ({(file, rule): starts}, info) with info as
+    scan_device_raw's.  Tests only."""
+    import torch
+    L = _lib.lib()
+    data, offsets = pack(args_list)
+    eng = scanner.engine()
+    _lib.check(L.tsg_test_keep_gather(eng, 1))
+    d = torch.from_numpy(data).to(device)
+    torch.cuda.synchronize()
+    res = ctypes.c_void_p()
+    _lib.check(L.tsg_prefilter_resident(eng, ctypes.c_void_p(d.data_ptr()), None, offsets.ctypes.data, len(args_list),
+                                        ctypes.byref(res)))
+    try:
+        st = _lib.result_stats(res)
+        seg = {"f0": 0, "nfiles": len(args_list), "lead": 0, "chunk_bytes": st["chunk_bytes"], "b0": 0,
+               "bytes": int(offsets[-1]), "lead_bytes": 0, "gather": _gather_segment(res, 0)}
+        info = {"flags": _result_file_flags(res), "segments": [seg], "stats": st,
+                "gather_stats": _lib.result_gather_stats(res)}
+        return _result_candidates(res), info
+    finally:
+        L.tsg_result_free(res)
+        del d
+
+
+def gather_pool(scanner):
+    """(buffers, idle, bytes) of the engine's gather-buffer pools (tsg_test_gather_pool)."""
+    b, i, n = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint64()
+    _lib.check(_lib.lib().tsg_test_gather_pool(scanner.engine(), ctypes.byref(b), ctypes.byref(i), ctypes.byref(n)))
+    return b.value, i.value, n.value
 
 
 def plan_segments(offsets, resident=False, base=0, with_paths=True, **policy):
