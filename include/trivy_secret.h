@@ -188,8 +188,10 @@ int tsg_feed_probe(tsg_engine* e, const uint8_t* data, uint64_t bytes, double* m
  * uint64, nondecreasing, d_offsets[0] = 0, d_offsets[nfiles] = total (checked);
  * d_new_offsets: nfiles + 1 device uint64 receiving each file's start in
  * d_dst.  *out_total = stripped bytes (= d_new_offsets[nfiles]); *ms (may be
- * NULL) = kernel time.  Synchronous.  Binary files (ExtractPrintableBytes)
- * stay on the host path.  The scan to follow it is tsg_scan_batch_device on
+ * NULL) = kernel time.  Synchronous.  This is one line of Analyze for a batch
+ * the caller knows to be all text; tsg_prepare_batch_device (below) does the
+ * whole preparation, binaries included, for a raw batch of any files.  The
+ * scan to follow it is tsg_scan_batch_device on
  * d_dst with the host's copy of d_new_offsets (d_dst needs 16 readable bytes
  * past the stripped total): the stripped bytes never leave the device. */
 int tsg_strip_cr_device(tsg_engine* e, const void* d_src, const uint64_t* d_offsets, uint32_t nfiles,
@@ -282,6 +284,32 @@ typedef struct tsg_feed_opts {
 int tsg_prepare_batch_opts(const tsg_ruleset* rs, const uint8_t* raw, const uint64_t* raw_offsets, uint32_t nfiles,
                            const char* const* paths, const uint32_t* path_lens, const tsg_feed_opts* opts,
                            tsg_prepared** out);
+/* tsg_prepare_batch_opts for a raw batch that lives in HBM: the device twin of
+ * tsg_prepare_batch -> tsg_scan_batch is
+ *   tsg_prepare_batch_device -> tsg_scan_batch_device,
+ * for every kind of file.  d_raw: the files as read, back to back, on one of
+ * the engine's devices (read only below raw_offsets[nfiles]); raw_offsets,
+ * paths, path_lens: host arrays as for tsg_prepare_batch.  The gate (file
+ * patterns, Required) runs on the host from the paths and sizes, on
+ * opts->threads threads; of opts only config_path, file_patterns and threads
+ * are used (NULL: defaults); the rule set is the engine's.  One device pass
+ * then does Analyze's content preparation: IsBinary on every file's first 300
+ * bytes, binaries other than .pyc dropped, CR stripped from text,
+ * ExtractPrintableBytes for binary .pyc files, the kept contents packed back
+ * to back at d_dst followed by 64 zero bytes.  d_raw and d_dst are 16-byte
+ * aligned and do not overlap; dst_cap = bytes at d_dst.  The prepared bytes
+ * never exceed raw_offsets[nfiles] + (number of .pyc paths), so that + 64
+ * always suffices; with less, a batch that does not fit fails with
+ * TSG_ERR_INVALID, the size needed in the message and d_dst untouched.
+ * *out: an ordinary tsg_prepared whose tsg_prepared_view gives offsets, index,
+ * binary and nkept of the kept files and data == NULL (the bytes are at
+ * d_dst).  *ms (may be NULL) = kernel time.  Synchronous.  The scan to follow
+ * is tsg_scan_batch_device(e, d_dst, offsets, nkept, <kept paths>, ...,
+ * binary, ...): nothing of the contents crosses the link before the
+ * confirmer's gather. */
+int tsg_prepare_batch_device(tsg_engine* e, const void* d_raw, const uint64_t* raw_offsets, uint32_t nfiles,
+                             const char* const* paths, const uint32_t* path_lens, const tsg_feed_opts* opts,
+                             void* d_dst, uint64_t dst_cap, tsg_prepared** out, double* ms);
 /* tsg_prepare_layer_tar with feed options. */
 int tsg_prepare_layer_tar_opts(const tsg_ruleset* rs, const uint8_t* tar, size_t len, const tsg_feed_opts* opts,
                                tsg_prepared** out);

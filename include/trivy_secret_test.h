@@ -131,6 +131,27 @@ int tsg_scan_device_model_release(const tsg_ruleset* rs, const uint8_t* data, co
                                   const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
                                   uint32_t chunk, void (*release)(void* user), void* user, tsg_result** out);
 
+/* CPU model of tsg_prepare_batch_device (csrc/prep.h: plan_prep, the device
+ * pass stated sequentially with its per-byte rule: a byte of a binary .pyc is
+ * kept iff it is printable and lies in a window of 5 printable bytes of its
+ * file, and a '\n' follows a kept byte whose successor is not printable or is
+ * the file's end) behind the same host gate.  *out is an ordinary
+ * tsg_prepared with the bytes on the host; kinds (nfiles bytes, may be NULL)
+ * receives 0 dropped / 1 text / 2 printable runs per raw file, new_offsets
+ * (nfiles + 1, may be NULL) every raw file's start in the prepared bytes.
+ * Tests only; the independent restatement it is checked against is
+ * tsg_prepare_batch_opts. */
+int tsg_prepare_device_model(const tsg_ruleset* rs, const uint8_t* raw, const uint64_t* raw_offsets, uint32_t nfiles,
+                             const char* const* paths, const uint32_t* path_lens, const tsg_feed_opts* opts,
+                             uint8_t* kinds, uint64_t* new_offsets, tsg_prepared** out);
+/* The device pass's printable table (re::is_print of the 256 byte values) as
+ * 256 bytes of 0 / 1.  Tests only. */
+int tsg_prepare_print_table(uint8_t* table);
+/* Measurement hook: the kernel times (ms) of the four passes of the
+ * tsg_prepare_batch_device call that made p -- classify, count, scan,
+ * compact (tools/prep_probe.py). */
+int tsg_prepared_pass_ms(const tsg_prepared* p, double* pass_ms);
+
 /* Bit of a file's flag word (engine.h kFileFoldSpecial): the file holds
  * U+0130, U+212A or U+017F, so the host scans it with the variant tables.  K1
  * may also set it for a file that shares a 16-byte word of the batch with such

@@ -204,6 +204,15 @@ SIGNATURES += [
                                                   ctypes.POINTER(TsgFeedOpts), ctypes.POINTER(ctypes.c_void_p)]),
     ("tsg_prepare_fs_tree", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(TsgFeedOpts),
                                            ctypes.POINTER(ctypes.c_void_p)]),
+    ("tsg_prepare_batch_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(TsgFeedOpts),
+                                                ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p),
+                                                ctypes.POINTER(ctypes.c_double)]),
+    ("tsg_prepare_device_model", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(TsgFeedOpts),
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    ("tsg_prepare_print_table", ctypes.c_int, [ctypes.c_void_p]),
+    ("tsg_prepared_pass_ms", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
 ]
 
 # tsg_read_fn: int64_t (*)(void* user, uint8_t* buf, size_t cap)

@@ -24,6 +24,7 @@
 #include "feed.h"
 #include "tar.h"
 #include "prefilter.h"
+#include "prep.h"
 #include "report.h"
 #include "queue.h"
 #include "stream.h"
@@ -74,6 +75,7 @@ struct tsg_prepared {
   std::vector<const char*> path_ptrs;
   std::vector<uint32_t> path_lens;
   std::string walk_json;
+  double pass_ms[4] = {0, 0, 0, 0};   // tsg_prepare_batch_device: kernel time of classify, count, scan, compact
 };
 
 struct tsg_result {
@@ -1399,6 +1401,99 @@ int tsg_prepare_batch_opts(const tsg_ruleset* rs, const uint8_t* raw, const uint
     return fail(TSG_ERR_INVALID, err);
   }
   *out = p;
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+namespace {
+// The kept files of a device-style preparation: a dropped file has zero
+// length in new_off, so the kept offsets are picked from the per-file starts.
+void kept_from_kinds(const std::vector<uint8_t>& kinds, const std::vector<uint64_t>& new_off, PreparedBatch* b) {
+  b->index.clear();
+  b->binary.clear();
+  b->offsets.clear();
+  for (uint32_t i = 0; i < kinds.size(); ++i) {
+    if (kinds[i] == kPrepDropped) continue;
+    b->index.push_back(i);
+    b->binary.push_back(kinds[i] == kPrepPrintable);
+    b->offsets.push_back(new_off[i]);
+  }
+  b->offsets.push_back(new_off[kinds.size()]);
+}
+}  // namespace
+
+int tsg_prepare_batch_device(tsg_engine* e, const void* d_raw, const uint64_t* raw_offsets, uint32_t nfiles,
+                             const char* const* paths, const uint32_t* path_lens, const tsg_feed_opts* opts,
+                             void* d_dst, uint64_t dst_cap, tsg_prepared** out, double* ms) {
+  TSG_API_TRY
+  if (!e || !out || !raw_offsets || (nfiles && !paths)) return fail(TSG_ERR_INVALID, "NULL argument");
+  FeedOpts fo;
+  std::vector<std::string> sf, sd;
+  int nt;
+  bool pinned;
+  std::string err;
+  if (!feed_opts(opts, &fo, &sf, &sd, &nt, &pinned, &err)) return fail(TSG_ERR_INVALID, err);
+  for (uint32_t i = 0; i < nfiles; ++i)
+    if (raw_offsets[i + 1] < raw_offsets[i]) return fail(TSG_ERR_INVALID, "offsets must be non-decreasing");
+  std::vector<uint8_t> flags(nfiles), kinds(nfiles);
+  std::vector<uint64_t> new_off(static_cast<size_t>(nfiles) + 1);
+  prepare_gate(*e->eng->ruleset(), fo, raw_offsets, nfiles, paths, path_lens, nt, flags.data());
+  auto p = std::make_unique<tsg_prepared>();
+  uint64_t total = 0;
+  if (!e->eng->prepare_device(d_raw, raw_offsets, nfiles, flags.data(), d_dst, dst_cap, new_off.data(), kinds.data(),
+                              &total, ms, p->pass_ms, &err))
+    return fail(err.find("device preparation:") == 0 ? TSG_ERR_INVALID : TSG_ERR_HIP, err);
+  kept_from_kinds(kinds, new_off, &p->b);
+  *out = p.release();
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_prepare_device_model(const tsg_ruleset* rs, const uint8_t* raw, const uint64_t* raw_offsets, uint32_t nfiles,
+                             const char* const* paths, const uint32_t* path_lens, const tsg_feed_opts* opts,
+                             uint8_t* kinds, uint64_t* new_offsets, tsg_prepared** out) {
+  TSG_API_TRY
+  if (!rs || !out || !raw_offsets || (nfiles && (!raw || !paths))) return fail(TSG_ERR_INVALID, "NULL argument");
+  FeedOpts fo;
+  std::vector<std::string> sf, sd;
+  int nt;
+  bool pinned;
+  std::string err;
+  if (!feed_opts(opts, &fo, &sf, &sd, &nt, &pinned, &err)) return fail(TSG_ERR_INVALID, err);
+  if (raw_offsets[0] != 0) return fail(TSG_ERR_INVALID, "offsets must start at 0");
+  for (uint32_t i = 0; i < nfiles; ++i)
+    if (raw_offsets[i + 1] < raw_offsets[i]) return fail(TSG_ERR_INVALID, "offsets must be non-decreasing");
+  std::vector<uint8_t> flags(nfiles);
+  prepare_gate(*rs->rs, fo, raw_offsets, nfiles, paths, path_lens, nt, flags.data());
+  PrepPlan plan;
+  plan_prep(raw, raw_offsets, nfiles, flags.data(), &plan);
+  auto p = std::make_unique<tsg_prepared>();
+  kept_from_kinds(plan.kinds, plan.new_off, &p->b);
+  const size_t n = plan.out.size();
+  p->b.data = std::shared_ptr<uint8_t>(new uint8_t[n + 64], std::default_delete<uint8_t[]>());
+  if (n) std::memcpy(p->b.data.get(), plan.out.data(), n);
+  std::memset(p->b.data.get() + n, 0, 64);
+  if (kinds && nfiles) std::memcpy(kinds, plan.kinds.data(), nfiles);
+  if (new_offsets) std::memcpy(new_offsets, plan.new_off.data(), plan.new_off.size() * 8);
+  *out = p.release();
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_prepare_print_table(uint8_t* table) {
+  TSG_API_TRY
+  if (!table) return fail(TSG_ERR_INVALID, "NULL argument");
+  uint32_t tab[8];
+  prep_print_table(tab);
+  for (uint32_t b = 0; b < 256; ++b) table[b] = (tab[b >> 5] >> (b & 31)) & 1u;
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_prepared_pass_ms(const tsg_prepared* p, double* pass_ms) {
+  TSG_API_TRY
+  if (!p || !pass_ms) return fail(TSG_ERR_INVALID, "NULL argument");
+  for (int i = 0; i < 4; ++i) pass_ms[i] = p->pass_ms[i];
   return TSG_OK;
   TSG_API_CATCH
 }

@@ -140,6 +140,18 @@ class Engine {
   bool strip_cr(const void* d_src, const uint64_t* d_off, uint32_t nfiles, uint64_t total, void* d_dst,
                 uint64_t* d_new_off, uint64_t* out_total, double* ms, std::string* err);
 
+  // GPU-side content preparation of a raw device-resident batch (prep.hip;
+  // prep.h is its CPU model) on the device that owns d_raw: h_off (host,
+  // nfiles + 1, nondecreasing from 0) cuts it into files, h_flags (host) are
+  // prepare_gate's.  d_dst (dst_cap bytes) receives the prepared bytes and 64
+  // zero bytes; h_new_off (nfiles + 1) every file's start in it, h_kinds
+  // (nfiles) what became of each file.  Fails, with the size needed in *err
+  // and d_dst untouched, when they do not fit.  pass_ms (may be NULL): the
+  // kernel time of classify, count, scan, compact; *ms their sum.
+  bool prepare_device(const void* d_raw, const uint64_t* h_off, uint32_t nfiles, const uint8_t* h_flags, void* d_dst,
+                      uint64_t dst_cap, uint64_t* h_new_off, uint8_t* h_kinds, uint64_t* out_total, double* ms,
+                      double* pass_ms, std::string* err);
+
   // Lanes created over all devices, call contexts, and confirm-pool threads
   // started (test hook: the per-file queue's footprint).
   void footprint(uint32_t* lanes, uint32_t* calls, uint32_t* pool_threads);

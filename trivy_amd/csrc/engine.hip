@@ -1668,6 +1668,7 @@ struct Lane : LaneStreams {
   DevBuf<unsigned long long> d_k2s;    // TSG_K2_STATS: per-rule K2 counters (4 per rule)
   DevBuf<unsigned int> d_cnt;
   DevBuf<uint8_t> d_cr;                // CR strip scratch (crstrip.hip)
+  DevBuf<uint8_t> d_prep;              // raw-batch preparation scratch (prep.hip)
   // device-only scans (gather.hip): per-file need flags and gather offsets,
   // the run table, [runs, gather_total]; their readbacks; the gather buffer
   // size the lane's last segment ended with
@@ -3355,6 +3356,84 @@ bool Engine::strip_cr(const void* d_src, const uint64_t* d_off, uint32_t nfiles,
   }
   if (out_total) *out_total = stripped;
   if (ms) *ms = kms;
+  return true;
+}
+
+}  // namespace tsg
+#include "prep_dev.h"   // (this file's include block belongs to K1's build hash)
+namespace tsg {
+
+bool Engine::prepare_device(const void* d_raw, const uint64_t* h_off, uint32_t nfiles, const uint8_t* h_flags,
+                            void* d_dst, uint64_t dst_cap, uint64_t* h_new_off, uint8_t* h_kinds, uint64_t* out_total,
+                            double* ms, double* pass_ms, std::string* err) {
+  if (!h_off || !h_new_off || (nfiles && (!h_flags || !h_kinds))) { *err = "device preparation: null argument"; return false; }
+  if (h_off[0] != 0) { *err = "device preparation: offsets must start at 0"; return false; }
+  for (uint32_t i = 0; i < nfiles; ++i)
+    if (h_off[i + 1] < h_off[i]) { *err = "device preparation: offsets must be non-decreasing"; return false; }
+  const uint64_t total = h_off[nfiles];
+  if ((total && !d_raw) || (dst_cap && !d_dst)) { *err = "device preparation: null buffer"; return false; }
+  if ((reinterpret_cast<uintptr_t>(d_raw) | reinterpret_cast<uintptr_t>(d_dst)) & 15u) {
+    *err = "device preparation: buffers must be 16-byte aligned";
+    return false;
+  }
+  const uintptr_t ra = reinterpret_cast<uintptr_t>(d_raw), da = reinterpret_cast<uintptr_t>(d_dst);
+  if (total && dst_cap && ra < da + dst_cap && da < ra + total) {
+    *err = "device preparation: d_raw and d_dst must not overlap";
+    return false;
+  }
+  // both buffers must be memory of one device the engine spans; the kernels
+  // run there (an engine over several devices takes the buffers' device)
+  const int dev = total ? device_of(d_raw) : dst_cap ? device_of(d_dst) : dev_[0]->device;
+  DeviceTables* dtp = nullptr;
+  for (auto& d : dev_) if (d->device == dev) { dtp = d.get(); break; }
+  if (!dtp || (dst_cap && device_of(d_dst) != dev)) {
+    *err = "device preparation: buffers must be device memory of one of the engine's devices";
+    return false;
+  }
+  DeviceTables& dt = *dtp;
+  Lane* ln = acquire_lane(dt, err);
+  if (!ln) return false;
+  bool ok = hipSetDevice(dt.device) == hipSuccess;
+  ok = ok && ln->d_prep.ensure(prep_scratch_bytes(total, nfiles), err);
+  PrepScratch sc{};
+  uint32_t tab[8];
+  prep_print_table(tab);
+  if (ok) {
+    sc = prep_scratch_layout(ln->d_prep.p, total, nfiles);
+    ok = hipMemcpyAsync(sc.offsets, h_off, (static_cast<size_t>(nfiles) + 1) * 8, hipMemcpyHostToDevice,
+                        ln->compute) == hipSuccess &&
+         hipMemcpyAsync(sc.print_tab, tab, sizeof tab, hipMemcpyHostToDevice, ln->compute) == hipSuccess &&
+         (!nfiles || hipMemcpyAsync(sc.flags, h_flags, nfiles, hipMemcpyHostToDevice, ln->compute) == hipSuccess);
+  }
+  if (ok && !ln->gev[0]) ok = hipEventCreate(&ln->gev[0]) == hipSuccess;   // (a device-only scan makes both)
+  hipEvent_t pev[5] = {ln->ev[0], ln->ev[1], ln->ev[2], ln->ev[3], ln->gev[0]};
+  ok = ok && prep_launch(static_cast<const uint8_t*>(d_raw), total, nfiles, static_cast<uint8_t*>(d_dst), dst_cap, sc,
+                         ln->compute, pev, err);
+  uint64_t prepared = 0;
+  ok = ok && hipMemcpyAsync(&prepared, sc.total, 8, hipMemcpyDeviceToHost, ln->compute) == hipSuccess &&
+       hipMemcpyAsync(h_new_off, sc.new_off, (static_cast<size_t>(nfiles) + 1) * 8, hipMemcpyDeviceToHost,
+                      ln->compute) == hipSuccess &&
+       (!nfiles || hipMemcpyAsync(h_kinds, sc.kinds, nfiles, hipMemcpyDeviceToHost, ln->compute) == hipSuccess) &&
+       hipStreamSynchronize(ln->compute) == hipSuccess;
+  double pm[4] = {0, 0, 0, 0};
+  for (int i = 0; i < 4 && ok; ++i) {
+    float f = 0;
+    ok = hipEventElapsedTime(&f, pev[i], pev[i + 1]) == hipSuccess;
+    pm[i] = f;
+  }
+  release_lane(dt, ln);
+  if (!ok) {
+    if (err->empty()) *err = "device preparation failed on the device";
+    return false;
+  }
+  if (out_total) *out_total = prepared;
+  if (prepared + 64 > dst_cap) {
+    *err = "device preparation: d_dst is too small: " + std::to_string(prepared + 64) + " bytes needed, " +
+           std::to_string(dst_cap) + " given";
+    return false;
+  }
+  if (ms) *ms = pm[0] + pm[1] + pm[2] + pm[3];
+  if (pass_ms) for (int i = 0; i < 4; ++i) pass_ms[i] = pm[i];
   return true;
 }
 

@@ -193,6 +193,16 @@ int secret_analyzer_wants_path(const Ruleset& rs, const FeedOpts& opts, const st
   return required_path(rs, clean, go_base(opts.config_path)) ? 2 : 0;
 }
 
+void prepare_gate(const Ruleset& rs, const FeedOpts& opts, const uint64_t* raw_off, uint32_t nfiles,
+                  const char* const* paths, const uint32_t* path_lens, int threads, uint8_t* flags) {
+  const std::string cfg_base = go_base(opts.config_path);
+  parallel_for(nfiles, threads, [&](uint32_t i) {
+    const std::string path = path_lens ? std::string(paths[i], path_lens[i]) : std::string(paths[i]);
+    const bool gate = opts.assume_required || wants(rs, opts, path, raw_off[i + 1] - raw_off[i], cfg_base);
+    flags[i] = static_cast<uint8_t>((gate ? 1 : 0) | (go_ext(path) == ".pyc" ? 2 : 0));
+  });
+}
+
 bool prepare_batch(const Ruleset& rs, const std::string& config_path, const uint8_t* raw, const uint64_t* raw_off,
                    uint32_t nfiles, const char* const* paths, const uint32_t* path_lens, int threads,
                    PreparedBatch* out, std::string* err, FeedAlloc alloc) {

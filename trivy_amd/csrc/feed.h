@@ -38,6 +38,13 @@ bool secret_analyzer_wants(const Ruleset& rs, const FeedOpts& opts, const std::s
 // wanted by a file pattern (any size), 2 = wanted if size >= 10 (Required).
 int secret_analyzer_wants_path(const Ruleset& rs, const FeedOpts& opts, const std::string& path);
 
+// The host's part of the device-side preparation (prep.h): per file, bit 0
+// (kPrepGate) = the gate above on (path, raw_off[i + 1] - raw_off[i]), bit 1
+// (kPrepAllowed) = allowedBinary (filepath.Ext(path) == ".pyc"); the
+// contents are not read.  flags: nfiles bytes.
+void prepare_gate(const Ruleset& rs, const FeedOpts& opts, const uint64_t* raw_off, uint32_t nfiles,
+                  const char* const* paths, const uint32_t* path_lens, int threads, uint8_t* flags);
+
 // Output buffer for the packed contents: returns memory of `bytes` bytes and
 // sets the deleter, or nullptr (the batch then uses the heap).  An empty
 // FeedAlloc means the heap.

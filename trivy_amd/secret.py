@@ -172,6 +172,62 @@ class Scanner:
                                                    ctypes.byref(ms)))
         return dst, new_off, out_total.value, ms.value
 
+    def PrepareBatchDevice(self, d_raw, raw_offsets, paths, config_path="", file_patterns=(), image=False,
+                           threads=0, dst_cap=None, with_passes=False):
+        """The analyzer's whole content preparation on the GPU
+        (tsg_prepare_batch_device; pkg/fanal/analyzer/secret/secret.go:103-150)
+        for a raw batch that lives in HBM: the device twin of PrepareBatch.
+
+        d_raw: uint8 device tensor, the files as read, back to back (16-byte
+        aligned); raw_offsets: nfiles + 1 host integers (0 ... total); paths:
+        input.FilePath of every file.  The gate (file_patterns, Required with
+        config_path) runs on the host from the paths and sizes; the device
+        classifies every file by its first 300 bytes (utils.IsBinary), drops
+        binaries other than .pyc, strips CR from text and extracts the
+        printable runs of binary .pyc files (utils.ExtractPrintableBytes),
+        packing the kept contents into a new tensor of total + (number of .pyc
+        paths) + 64 bytes (dst_cap: another size, for tests).
+
+        Returns (d_dst, offsets, scan_paths, index, binary, kernel_ms) for the
+        kept files: offsets (nkept + 1, uint64) cut d_dst, index[k] is kept
+        file k's place in `paths`, scan_paths its ScanArgs.FilePath (image=True
+        adds the "/" prefix, secret.go:133-135), binary its ScanArgs.Binary.
+        with_passes appends the kernel times of classify, count, scan, compact.
+        The scan to follow is ScanBatchDevice(d_dst, offsets, scan_paths, binary)."""
+        import torch
+        L = _lib.lib()
+        off = np.ascontiguousarray(raw_offsets, dtype=np.uint64)
+        nfiles = len(off) - 1
+        if nfiles != len(paths):
+            raise ValueError("raw_offsets must hold one more entry than paths")
+        total = int(off[-1]) if nfiles else 0
+        if d_raw.dtype != torch.uint8 or not d_raw.is_cuda or not d_raw.is_contiguous():
+            raise ValueError("d_raw must be a contiguous uint8 device tensor")
+        if d_raw.numel() < total:
+            raise ValueError("d_raw is shorter than the batch")
+        enc = [p.encode("utf-8", "surrogateescape") if isinstance(p, str) else bytes(p) for p in paths]
+        if dst_cap is None:
+            dst_cap = total + sum(1 for p in enc if p.endswith(b".pyc")) + 64
+        dst = torch.empty(max(int(dst_cap), 16), dtype=torch.uint8, device=d_raw.device)
+        cpaths, lens, _keep = _lib.pack_paths(enc)
+        o, keep = _lib.feed_opts(config_path, file_patterns, threads=threads)
+        torch.cuda.current_stream(d_raw.device).synchronize()     # the engine runs on its own stream
+        h, ms = ctypes.c_void_p(), ctypes.c_double()
+        rc = L.tsg_prepare_batch_device(self.engine(), ctypes.c_void_p(d_raw.data_ptr()), off.ctypes.data, nfiles,
+                                        cpaths, lens, ctypes.byref(o), ctypes.c_void_p(dst.data_ptr()), int(dst_cap),
+                                        ctypes.byref(h), ctypes.byref(ms))
+        del keep
+        _lib.check(rc)
+        try:
+            offs, idx, binf, _data = _prepared_view(L, h)
+            passes = (ctypes.c_double * 4)()
+            _lib.check(L.tsg_prepared_pass_ms(h, passes))
+        finally:
+            L.tsg_prepared_free(h)
+        scan_paths = [("/" if image else "") + paths[i] for i in idx]
+        out = (dst, offs, scan_paths, idx, binf, ms.value)
+        return out + (list(passes),) if with_passes else out
+
     def Scan(self, args):
         return self.ScanBatch([args])[0]
 
@@ -256,12 +312,19 @@ class Scanner:
         synchronised first.  with_stats adds the scan's stats and the gather's
         (gather_files, gather_bytes, gather_runs, gather_ms, gather_retries).
 
-        The chain for files uploaded as read, CRLF line ends included:
+        The chain for files uploaded as read, of any kind (CRLF text, binaries
+        to drop, binary .pyc files), is PrepareBatchDevice -> ScanBatchDevice,
+        the device twin of PrepareBatch -> ScanBatch:
+
+            dst, off, scan_paths, index, binary, _ = sc.PrepareBatchDevice(d_raw, raw_offsets, paths)
+            found = sc.ScanBatchDevice(dst, off, scan_paths, binary)
+
+        -- found[k] belongs to paths[index[k]]; the prepared bytes stay on the
+        device, only offsets and flags come back.  For a batch known to be all
+        text, StripCR alone does the content preparation:
 
             dst, new_off, total, _ = sc.StripCR(d_raw, d_raw_offsets, nfiles, raw_total)
-            found = sc.ScanBatchDevice(dst, new_off.cpu().numpy(), paths)
-
-        -- the stripped bytes stay on the device; only the offsets come back."""
+            found = sc.ScanBatchDevice(dst, new_off.cpu().numpy(), paths)"""
         return self._scan_device_tensor(d_data, offsets, paths, binary, None, with_stats)
 
     def ScanBatchResident(self, d_data, h_data, offsets, paths, binary=None, with_stats=False):
@@ -380,6 +443,58 @@ def PrepareLayerTar(scanner, tar, skip_files=(), skip_dirs=(), config_path="", t
         return out, walk, secrets
     finally:
         L.tsg_prepared_free(h)
+
+
+def _prepared_view(L, h):
+    """(offsets uint64 array, index list, binary list, bytes or None) of a
+    tsg_prepared handle; the bytes are None for a device preparation."""
+    d, o, ix, b = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+    nk = ctypes.c_uint32()
+    _lib.check(L.tsg_prepared_view(h, ctypes.byref(d), ctypes.byref(o), ctypes.byref(ix), ctypes.byref(b),
+                                   ctypes.byref(nk)))
+    n = nk.value
+    offs = np.ctypeslib.as_array(ctypes.cast(o, ctypes.POINTER(ctypes.c_uint64)), shape=(n + 1,)).copy()
+    idx = np.ctypeslib.as_array(ctypes.cast(ix, ctypes.POINTER(ctypes.c_uint32)), shape=(n,)).tolist() if n else []
+    binf = np.ctypeslib.as_array(ctypes.cast(b, ctypes.POINTER(ctypes.c_uint8)), shape=(n,)).tolist() if n else []
+    data = ctypes.string_at(d, int(offs[-1])) if d.value else None
+    return offs, idx, binf, data
+
+
+def prepare_batch_view(scanner, files, config_path="", file_patterns=(), model=False):
+    """tsg_prepare_batch_opts (model=False) or the CPU model of the device
+    preparation, tsg_prepare_device_model (model=True), on files = [(path,
+    raw bytes)] as plain arrays: {"offsets", "index", "binary", "data"}; the
+    model adds "kinds" (per raw file) and "new_offsets" (nfiles + 1).  Tests."""
+    L = _lib.lib()
+    raw, offsets = pack([ScanArgs(p, c) for p, c in files])
+    paths, lens, _keep = _lib.pack_paths([p for p, _ in files])
+    o, keep = _lib.feed_opts(config_path, file_patterns)
+    h = ctypes.c_void_p()
+    out = {}
+    if model:
+        kinds = np.zeros(max(len(files), 1), np.uint8)
+        new_off = np.zeros(len(files) + 1, np.uint64)
+        _lib.check(L.tsg_prepare_device_model(scanner._rs, raw.ctypes.data, offsets.ctypes.data, len(files), paths,
+                                              lens, ctypes.byref(o), kinds.ctypes.data, new_off.ctypes.data,
+                                              ctypes.byref(h)))
+        out["kinds"] = kinds[:len(files)].tolist()
+        out["new_offsets"] = new_off
+    else:
+        _lib.check(L.tsg_prepare_batch_opts(scanner._rs, raw.ctypes.data, offsets.ctypes.data, len(files), paths,
+                                            lens, ctypes.byref(o), ctypes.byref(h)))
+    del keep
+    try:
+        out["offsets"], out["index"], out["binary"], out["data"] = _prepared_view(L, h)
+    finally:
+        L.tsg_prepared_free(h)
+    return out
+
+
+def prepare_print_table():
+    """The device preparation's printable table: 256 values of 0 / 1 (test hook)."""
+    t = (ctypes.c_uint8 * 256)()
+    _lib.check(_lib.lib().tsg_prepare_print_table(t))
+    return list(t)
 
 
 def _prepared_args(L, h, with_paths, paths_in=None):
