@@ -9,6 +9,10 @@ operation on the host (Python's bytes.replace / numpy), per file:
   CR, runs of tiny files inside one 1 KiB sub-tile, files spanning the
   kernel's 64 KiB regions, totals that are not a multiple of 16, batches
   without any CR (the aligned direct-store path) and dense CR;
+* the raw bytes of every corpus of tests/_prep_corpus.py, all files as text;
+* a hand-built batch with file starts, empty files and CRs on both sides of
+  1 KiB sub-tile and 64 KiB region edges, its total a multiple of 64 KiB, and
+  the same with 7 bytes behind it;
 * a 256 MB batch at CRLF density checked through numpy;
 * end to end: raw CRLF files uploaded as read, stripped on the GPU, the
   stripped bytes brought back and scanned resident equal Scan over the
@@ -19,6 +23,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import _prep_corpus as PC
 from trivy_amd import _lib
 from trivy_amd import secret as S
 
@@ -90,6 +95,78 @@ def test_strip_cr_matches_replace_gpu(kind):
     got = dst[:stripped].cpu().numpy().tobytes()
     assert got == b"".join(want)
     assert ms >= 0
+
+
+_cached = {}
+
+
+def _strip_and_check(files):
+    """Scanner.StripCR over the packed files: bytes, every new offset and the
+    total against per-file bytes.replace."""
+    import torch
+    if "scanner" not in _cached:
+        _cached["scanner"] = S.Scanner(None)
+    data, off = _pack(files)
+    d_src = torch.from_numpy(data.copy()).to("cuda:0")
+    d_off = torch.from_numpy(off.astype(np.int64)).to("cuda:0")
+    dst, new_off, stripped, _ms = _cached["scanner"].StripCR(d_src, d_off, len(files), int(off[-1]))
+    want = [f.replace(b"\r", b"") for f in files]
+    want_off = np.zeros(len(files) + 1, np.int64)
+    want_off[1:] = np.cumsum([len(w) for w in want])
+    assert stripped == int(want_off[-1])
+    assert np.array_equal(new_off.cpu().numpy(), want_off)
+    assert dst[:stripped].cpu().numpy().tobytes() == b"".join(want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", PC.NAMES)
+def test_strip_cr_prep_corpora_as_text_gpu(name):
+    """The raw bytes of every preparation corpus, all files taken as text (the
+    CR strip knows no kinds): the runs_*_edges corpora put file starts on
+    16-byte, 1 KiB and 64 KiB edges."""
+    if "corpora" not in _cached:
+        _cached["corpora"] = PC.corpora()
+    _strip_and_check([c for _, c in _cached["corpora"][name].raw_files])
+
+
+SUB, REGION = 1024, 64 * 1024
+# file starts of the hand-built batch: sub-tile edges (1024 k) next to and away
+# from region edges, and every region edge (65536 k) of three regions
+EDGES = (0, SUB, 2 * SUB, 7 * SUB, REGION - SUB, REGION, REGION + SUB, 2 * REGION - SUB, 2 * REGION, 3 * REGION - SUB)
+
+
+def _edge_batch(tail):
+    """3 x 64 KiB: at every edge of EDGES an empty file and the start of a file
+    whose first byte is '\\r', behind a file whose last byte is '\\r'; two empty
+    files at the batch end.  tail: 7 more bytes behind them (a ragged fourth region)."""
+    total = 3 * REGION
+    files = []
+    for a, b in zip(EDGES, EDGES[1:] + (total,)):
+        body = (b"line %d\r\nab\rc\n" % a) * ((b - a) // 12 + 1)
+        files += [b"", b"\r" + body[:b - a - 2] + b"\r"]
+    files += [b"", b""]
+    if tail:
+        files += [b"\rtail\r\r", b""]
+    return files
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tail", [False, True])
+def test_strip_cr_files_on_subtile_and_region_edges_gpu(tail):
+    files = _edge_batch(tail)
+    data, off = _pack(files)
+    starts = [int(o) for o in off[:-1]]
+    for e in EDGES + ((3 * REGION,) if tail else ()):
+        assert starts.count(e) >= 2                       # an empty file and a file's first byte
+        assert data[e] == 13 and (e == 0 or data[e - 1] == 13)
+    assert {0, REGION, 2 * REGION} <= set(EDGES) and all(e % SUB == 0 for e in EDGES)
+    assert {e for e in EDGES if e % REGION} >= {SUB, REGION - SUB, REGION + SUB}
+    if tail:
+        assert int(off[-1]) == 3 * REGION + 7 and starts.count(3 * REGION) == 3
+    else:
+        assert int(off[-1]) == 3 * REGION and data[3 * REGION - 1] == 13
+        assert [int(o) for o in off[-3:]] == [3 * REGION] * 3   # two empty files at the batch end
+    _strip_and_check(files)
 
 
 @pytest.mark.gpu

@@ -32,7 +32,7 @@ def demangle_short(name):
 def main():
     probe = "--probe" in sys.argv
     rows = []
-    for src in ("engine.hip", "crstrip.hip", "prep.hip"):
+    for src in ("engine.hip", "prep.hip"):
         cmd = ["hipcc", "-c", os.path.join(CSRC, src), "-o", "/dev/null", "--offload-arch=gfx950", "-x", "hip", "-O3",
                "-std=c++17", "-fPIC", "-I", CSRC, "-I", os.path.join(ROOT, "include"),
                "-Rpass-analysis=kernel-resource-usage"] + (["-DTSG_K1_PROBE"] if probe else [])

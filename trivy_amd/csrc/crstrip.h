@@ -1,4 +1,5 @@
-// GPU-side CR strip of a packed device batch.
+// GPU-side CR strip of a packed device batch (the kernels
+// are prep.hip's, with its scan skeleton).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -135,7 +135,7 @@ class Engine {
   bool feed_probe(const uint8_t* h_data, uint64_t bytes, double* ms, std::string* err);
 
   // GPU-side CR strip of a device-resident batch on the first device
-  // (crstrip.hip): d_dst = d_src without '\r', d_new_off = the files' new
+  // (crstrip.h, prep.hip): d_dst = d_src without '\r', d_new_off = the files' new
   // starts; *out_total = stripped bytes, *ms = the kernels' time (HIP events).
   bool strip_cr(const void* d_src, const uint64_t* d_off, uint32_t nfiles, uint64_t total, void* d_dst,
                 uint64_t* d_new_off, uint64_t* out_total, double* ms, std::string* err);
@@ -218,6 +218,7 @@ class Engine {
                        uint64_t* nfind, bool gpu_in_flight);
   Lane* acquire_lane(DeviceTables& dt, std::string* err);
   void release_lane(DeviceTables& dt, Lane* ln);
+  DeviceTables* tables_of(int device);                   // NULL: not one of the engine's devices
   CallCtx* acquire_call();
   void release_call(CallCtx* cc);
 

@@ -1667,7 +1667,7 @@ struct Lane : LaneStreams {
   DevBuf<uint32_t> d_fidx;             // K1's file index (tsg_file_index): one entry per 64 KiB
   DevBuf<unsigned long long> d_k2s;    // TSG_K2_STATS: per-rule K2 counters (4 per rule)
   DevBuf<unsigned int> d_cnt;
-  DevBuf<uint8_t> d_cr;                // CR strip scratch (crstrip.hip)
+  DevBuf<uint8_t> d_cr;                // CR strip scratch (crstrip.h)
   DevBuf<uint8_t> d_prep;              // raw-batch preparation scratch (prep.hip)
   // device-only scans (gather.hip): per-file need flags and gather offsets,
   // the run table, [runs, gather_total]; their readbacks; the gather buffer
@@ -3311,6 +3311,11 @@ bool Engine::feed_probe(const uint8_t* h_data, uint64_t bytes, double* ms, std::
   return ok;
 }
 
+DeviceTables* Engine::tables_of(int device) {
+  for (auto& d : dev_) if (d->device == device) return d.get();
+  return nullptr;
+}
+
 bool Engine::strip_cr(const void* d_src, const uint64_t* d_off, uint32_t nfiles, uint64_t total, void* d_dst,
                       uint64_t* d_new_off, uint64_t* out_total, double* ms, std::string* err) {
   if ((reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_dst)) & 15u) {
@@ -3321,8 +3326,7 @@ bool Engine::strip_cr(const void* d_src, const uint64_t* d_off, uint32_t nfiles,
   // every buffer must be memory of one device the engine spans; the kernels
   // run there (an engine over several devices takes the caller's device)
   const int dev = device_of(d_off);
-  DeviceTables* dtp = nullptr;
-  for (auto& d : dev_) if (d->device == dev) { dtp = d.get(); break; }
+  DeviceTables* dtp = tables_of(dev);
   if (!dtp || device_of(d_new_off) != dev || (total && (device_of(d_src) != dev || device_of(d_dst) != dev))) {
     *err = "CR strip buffers must be device memory of one of the engine's devices";
     return false;
@@ -3384,8 +3388,7 @@ bool Engine::prepare_device(const void* d_raw, const uint64_t* h_off, uint32_t n
   // both buffers must be memory of one device the engine spans; the kernels
   // run there (an engine over several devices takes the buffers' device)
   const int dev = total ? device_of(d_raw) : dst_cap ? device_of(d_dst) : dev_[0]->device;
-  DeviceTables* dtp = nullptr;
-  for (auto& d : dev_) if (d->device == dev) { dtp = d.get(); break; }
+  DeviceTables* dtp = tables_of(dev);
   if (!dtp || (dst_cap && device_of(d_dst) != dev)) {
     *err = "device preparation: buffers must be device memory of one of the engine's devices";
     return false;

@@ -2,27 +2,43 @@
 // preparation (pkg/fanal/analyzer/secret/secret.go:103-150) as one stream
 // compaction -- IsBinary on every file's head, binaries that are not allowed
 // dropped, '\r' stripped from text, ExtractPrintableBytes for allowed binaries
-// (prep.h states the per-byte rule and is the CPU model of this file).
+// (prep.h states the per-byte rule and is the CPU model of this file) -- and
+// its special case, the CR strip of a batch that is all text (SURVEY.md 8f
+// row 1, secret.go:121; crstrip.h).  Neither moves a byte across a file
+// boundary, so the batch's image is one stream compaction of the whole batch
+// and a file's new start is the output position of its first input byte.
 //
-// The shape is crstrip.hip's reduce / scan / compact over 64 KiB regions (one
-// wave each, 1 KiB sub-tiles, lane l holds bytes [16l, 16l + 16)), with the
-// per-byte emit count 0, 1 or 2 in place of "not '\r'":
+// Reduce / scan / compact over 64 KiB regions (one wave each, 1 KiB
+// sub-tiles, lane l holds bytes [16l, 16l + 16)); a byte emits 0, 1 or 2:
 //   tsg_prep_classify   kind[f] from the host's gate / allowed flags and the file's head
 //   tsg_prep_first      per region, the first file that starts after its first byte
 //   tsg_prep_pass<0>    bytes each region emits                         reads N
-//   tsg_prep_scan       exclusive prefix; the total; the 64 zero bytes behind it
+//   tsg_prep_scan       exclusive prefix; the total; the new start (0) of the
+//                       files at byte 0; the 64 zero bytes behind the output
 //   tsg_prep_pass<1>    the emitted bytes to their place, and the new start
 //                       of every file starting in (region start, region end]   reads N, writes N'
-// A sub-tile inside one text file is the CR strip's path unchanged (cr mask,
-// wave prefix sum, staged aligned stores; direct 16-byte stores while nothing
-// is removed).  Inside one allowed binary it is mask arithmetic on the 16
-// printable bits of a lane's word and 4 halo bits from each neighbour (the
-// sub-tile's own halo comes from the previous and the prefetched next word,
-// loaded only at region edges).  A sub-tile that holds file boundaries but
-// only text (or empty) files is the CR strip's again.  Only a sub-tile with a
+// The CR strip runs tsg_cr_count and tsg_cr_compact in place of the two
+// passes (no classify, no kinds: 52 VGPRs against 78, 8 waves per SIMD
+// against 6, 0.67 ms against 0.76 ms on 1 GB of text in 40k files) and
+// shares everything else.  HBM traffic 2N + N' (algorithmic
+// N + N').  A single-pass decoupled look-back variant (32 KiB workgroup
+// tiles, 512-tile window) was measured slower: 8.1 ms vs 6.1 ms for 10 GB
+// (DESIGN.md 4.2).
+//
+// A sub-tile of text: the kept ("not '\r'") counts' wave prefix sum places
+// each lane's bytes, and the sub-tile's output goes to HBM as aligned dwords
+// through a per-wave LDS staging line (byte stores only at the two partial
+// dwords at its ends, which neighbouring sub-tiles complete); a sub-tile
+// that loses nothing and whose output is 16-byte aligned (every one before
+// the batch's first '\r') is stored directly.  File boundaries between text
+// (or empty) files change nothing.  Inside one allowed binary it is mask
+// arithmetic on the 16 printable bits of a lane's word and 4 halo bits from
+// each neighbour (the sub-tile's own halo comes from the previous and the
+// prefetched next word, loaded only at region edges).  Only a sub-tile with a
 // boundary next to a dropped or an allowed-binary file looks files up: each
 // lane finds the file of its word's first byte by binary search and walks
 // the file pieces of its 16 bytes.
+#include "crstrip.h"
 #include "prep_dev.h"
 
 namespace tsg {
@@ -129,7 +145,10 @@ __global__ __launch_bounds__(256) void tsg_prep_first(const uint64_t* __restrict
 
 // One workgroup: region_base[r] = bytes emitted before region r; the total;
 // new_off of the files that start at byte 0 (every file of an empty batch);
-// the 64 zero bytes behind the prepared bytes, when they fit.
+// the 64 zero bytes behind the prepared bytes, when they fit (the CR strip
+// gives no dst: it writes no pad).  Each thread sums a contiguous run of
+// regions with its loads issued in groups of 8 (a one-at-a-time loop waits
+// one L2 round trip per region: 0.29 ms for 10 GB).
 __global__ __launch_bounds__(1024) void tsg_prep_scan(const uint32_t* __restrict__ region_n, uint32_t nregions,
                                                       uint64_t* __restrict__ region_base,
                                                       const uint64_t* __restrict__ offsets, uint32_t nfiles,
@@ -159,7 +178,17 @@ __global__ __launch_bounds__(1024) void tsg_prep_scan(const uint32_t* __restrict
     __syncthreads();
   }
   uint64_t run = part[t] - s;
-  for (i = b; i < e; ++i) {
+  for (i = b; i + 8 <= e; i += 8) {
+    uint32_t v[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = region_n[i + q];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      region_base[i + q] = run;
+      run += v[q];
+    }
+  }
+  for (; i < e; ++i) {
     region_base[i] = run;
     run += region_n[i];
   }
@@ -185,6 +214,134 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t lane) {
     if (lane >= d) v += u;
   }
   return v;
+}
+
+// Bytes that region [r0, r0 + kRegion) emits as text (in every lane)
+__device__ __forceinline__ uint32_t text_region_count(const uint8_t* __restrict__ src, uint64_t r0, uint64_t total,
+                                                      uint32_t lane) {
+  uint32_t n = 0;
+#pragma unroll 8
+  for (uint32_t j = 0; j < kRegion / kSub; ++j) {
+    uint32_t valid;
+    const v4u w = load16(src, r0 + j * kSub + lane * 16u, total, &valid);
+    n += __popc(valid & ~cr_mask16(w));
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) n += __shfl_xor(n, d);
+  return n;
+}
+
+// The bytes of w that `keep` names, to the staging line from lb[q] on
+__device__ __forceinline__ void stage_kept(uint8_t* lb, uint32_t q, v4u w, uint32_t keep) {
+  const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+  for (int b = 0; b < 16; ++b) {
+    if ((keep >> b) & 1u) {
+      lb[q] = static_cast<uint8_t>(ws[b >> 2] >> ((b & 3) * 8));
+      ++q;
+    }
+  }
+}
+
+// The wave's staging line (stage byte q holds output byte out - q0 + q, q0 =
+// out & 3) to dst[out, out + K): aligned dwords, bytes at the two ragged ends
+__device__ __forceinline__ void flush_stage(const uint8_t* lb, uint8_t* __restrict__ dst, uint64_t out, uint32_t q0,
+                                            uint32_t K, uint32_t lane) {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  const uint64_t a0 = out - q0, e = out + K;
+  const uint32_t ndw = static_cast<uint32_t>((e - a0 + 3) >> 2);
+  for (uint32_t d = lane; d < ndw; d += 64) {
+    const uint64_t g = a0 + 4ull * d;
+    const uint32_t v = *reinterpret_cast<const uint32_t*>(lb + 4 * d);
+    if (g >= out && g + 4 <= e) {
+      *reinterpret_cast<uint32_t*>(dst + g) = v;
+    } else {
+      for (uint32_t b = 0; b < 4; ++b)
+        if (g + b >= out && g + b < e) dst[g + b] = static_cast<uint8_t>(v >> (8 * b));
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// The files that start in (s0, s1] of a sub-tile at s0 whose output starts at
+// `out` (excl, keep, nl: each lane's; K: the sub-tile's bytes): new start =
+// output position of their first byte, out + K for a file at s0 + kSub.
+// *nf = the first file that starts after s0, *next_start its start; both
+// move past the files taken.
+template <bool kWrite>
+__device__ __forceinline__ void file_starts(const uint64_t* __restrict__ offsets, uint32_t nfiles, uint64_t s0,
+                                            uint64_t s1, uint64_t out, uint32_t excl, uint32_t keep, uint32_t nl,
+                                            uint32_t K, uint32_t lane, uint32_t* nf, uint64_t* next_start,
+                                            uint64_t* __restrict__ new_off) {
+  while (*next_start <= s1) {
+    const uint32_t idx = *nf + lane;
+    const uint64_t o = idx <= nfiles ? offsets[idx] : ~0ull;
+    const bool in = o <= s1;                // o > s0: files are sorted and nf is past the earlier ones
+    if (kWrite) {
+      const uint32_t rel = in ? static_cast<uint32_t>(o - s0) : 0u;
+      const bool inside = rel < kSub;
+      const uint32_t wi = inside ? rel >> 4 : 0u;
+      const uint32_t pe = __shfl(excl, wi), pk = __shfl(keep, wi), pn = __shfl(nl, wi);
+      const uint32_t below = (1u << (rel & 15u)) - 1u;
+      if (in) new_off[idx] = inside ? out + pe + __popc(pk & below) + __popc(pn & below) : out + K;
+    }
+    *nf += static_cast<uint32_t>(__popcll(__ballot(in)));
+    *next_start = *nf <= nfiles ? offsets[*nf] : ~0ull;
+  }
+}
+
+// The CR strip's passes: every file is text, so there are no kinds and no
+// file lookups.  region_n[r] = bytes region r keeps.
+__global__ __launch_bounds__(256) void tsg_cr_count(const uint8_t* __restrict__ src, uint64_t total, uint32_t nregions,
+                                                    uint32_t* __restrict__ region_n) {
+  const uint32_t lane = threadIdx.x & 63u, r = blockIdx.x * kWaves + (threadIdx.x >> 6);
+  if (r >= nregions) return;
+  const uint32_t n = text_region_count(src, static_cast<uint64_t>(r) * kRegion, total, lane);
+  if (lane == 0) region_n[r] = n;
+}
+
+// The kept bytes to dst from region_base[r] on, and new_off of the files that
+// start in (r0, r1].
+__global__ __launch_bounds__(256) void tsg_cr_compact(const uint8_t* __restrict__ src, uint64_t total,
+                                                      uint32_t nregions, const uint64_t* __restrict__ region_base,
+                                                      const uint32_t* __restrict__ first,
+                                                      const uint64_t* __restrict__ offsets, uint32_t nfiles,
+                                                      uint8_t* __restrict__ dst, uint64_t* __restrict__ new_off) {
+  __shared__ __attribute__((aligned(16))) uint8_t stage[kWaves][kSub + 16];
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint32_t r = blockIdx.x * kWaves + wv;
+  if (r >= nregions) return;                 // whole waves only; no workgroup barrier below
+  uint8_t* lb = stage[wv];
+  const uint64_t r0 = static_cast<uint64_t>(r) * kRegion;
+  const uint64_t r1 = min(r0 + kRegion, total);
+  uint64_t out = region_base[r];
+  uint32_t nf = first[r];                    // wave-uniform: the first file that starts after the sub-tile's first byte
+  uint64_t next_start = offsets[nf];
+  uint32_t valid_n;
+  v4u wn = load16(src, r0 + lane * 16u, total, &valid_n);
+  for (uint64_t s0 = r0; s0 < r1; s0 += kSub) {
+    const v4u w = wn;
+    const uint32_t valid = valid_n;
+    if (s0 + kSub < r1) wn = load16(src, s0 + kSub + lane * 16u, total, &valid_n);   // next sub-tile in flight
+    const uint32_t keep = valid & ~cr_mask16(w);
+    const uint32_t k = __popc(keep);
+    const uint32_t incl = wave_incl_scan(k, lane);
+    const uint32_t excl = incl - k;
+    const uint32_t K = __shfl(incl, 63);
+    const bool plain = __ballot(keep != 0xffffu) == 0;   // full sub-tile without '\r'
+    if (plain && (out & 15u) == 0) {
+      __builtin_nontemporal_store(w, reinterpret_cast<v4u*>(dst + out + lane * 16u));
+    } else if (K) {
+      const uint32_t q0 = static_cast<uint32_t>(out & 3u);
+      if (plain && q0 == 0) *reinterpret_cast<v4u*>(lb + lane * 16u) = w;
+      else stage_kept(lb, q0 + excl, w, keep);
+      flush_stage(lb, dst, out, q0, K, lane);
+    }
+    file_starts<true>(offsets, nfiles, s0, min(s0 + kSub, r1), out, excl, keep, 0u, K, lane, &nf, &next_start, new_off);
+    out += K;
+  }
 }
 
 // The 16 bytes at p taken as bytes of a file [fs, fe) of kind kd: bit b of
@@ -241,15 +398,7 @@ __global__ __launch_bounds__(256) void tsg_prep_pass(const uint8_t* __restrict__
   uint32_t kd = kinds[kf];
   uint64_t fs = offsets[kf];
   if (!kWrite && next_start >= r1 && kd == kPrepText) {      // the region lies in one text file
-    uint32_t n = 0;
-#pragma unroll 8
-    for (uint32_t j = 0; j < kRegion / kSub; ++j) {
-      uint32_t valid;
-      const v4u w = load16(src, r0 + j * kSub + lane * 16u, total, &valid);
-      n += __popc(valid & ~cr_mask16(w));
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) n += __shfl_xor(n, d);
+    const uint32_t n = text_region_count(src, r0, total, lane);
     if (lane == 0) region_n[r] = n;
     return;
   }
@@ -344,17 +493,11 @@ __global__ __launch_bounds__(256) void tsg_prep_pass(const uint8_t* __restrict__
         if (plain && q0 == 0) {
           *reinterpret_cast<v4u*>(lb + lane * 16u) = w;
         } else {
-          const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
           uint32_t q = q0 + excl;
           if (nl == 0) {
-#pragma unroll
-            for (int b = 0; b < 16; ++b) {
-              if ((keep >> b) & 1u) {
-                lb[q] = static_cast<uint8_t>(ws[b >> 2] >> ((b & 3) * 8));
-                ++q;
-              }
-            }
+            stage_kept(lb, q, w, keep);
           } else {
+            const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
 #pragma unroll
             for (int b = 0; b < 16; ++b) {
               if ((keep >> b) & 1u) {
@@ -368,40 +511,10 @@ __global__ __launch_bounds__(256) void tsg_prep_pass(const uint8_t* __restrict__
             }
           }
         }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        const uint64_t a0 = out - q0, e = out + K;
-        const uint32_t ndw = static_cast<uint32_t>((e - a0 + 3) >> 2);
-        for (uint32_t d = lane; d < ndw; d += 64) {
-          const uint64_t g = a0 + 4ull * d;
-          const uint32_t v = *reinterpret_cast<const uint32_t*>(lb + 4 * d);
-          if (g >= out && g + 4 <= e) {
-            *reinterpret_cast<uint32_t*>(dst + g) = v;
-          } else {
-            for (uint32_t b = 0; b < 4; ++b)
-              if (g + b >= out && g + b < e) dst[g + b] = static_cast<uint8_t>(v >> (8 * b));
-          }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        flush_stage(lb, dst, out, q0, K, lane);
       }
     }
-    // files starting in (s0, s1]: new start = output position of their first byte
-    while (next_start <= s1) {
-      const uint32_t idx = nf + lane;
-      const uint64_t o = idx <= nfiles ? offsets[idx] : ~0ull;
-      const bool in = o <= s1;                // o > s0: files are sorted and nf is past the earlier ones
-      if (kWrite) {
-        const uint32_t rel = in ? static_cast<uint32_t>(o - s0) : 0u;
-        const bool inside = rel < kSub;
-        const uint32_t wi = inside ? rel >> 4 : 0u;
-        const uint32_t pe = __shfl(excl, wi), pk = __shfl(keep, wi), pn = __shfl(nl, wi);
-        const uint32_t below = (1u << (rel & 15u)) - 1u;
-        if (in) new_off[idx] = inside ? out + pe + __popc(pk & below) + __popc(pn & below) : out + K;
-      }
-      nf += static_cast<uint32_t>(__popcll(__ballot(in)));
-      next_start = nf <= nfiles ? offsets[nf] : ~0ull;
-    }
+    file_starts<kWrite>(offsets, nfiles, s0, s1, out, excl, keep, nl, K, lane, &nf, &next_start, new_off);
     if (nf - 1 != kf && nf <= nfiles) {
       kf = nf - 1;
       kd = kinds[kf];
@@ -420,6 +533,33 @@ uint64_t prep_regions(uint64_t total) { return (total + kRegion - 1) / kRegion; 
 size_t align64(size_t n) { return (n + 63) & ~size_t(63); }
 
 }  // namespace
+
+size_t cr_strip_scratch_bytes(uint64_t total) { return 64 + prep_regions(total) * (8 + 4 + 4) + 64; }
+
+bool cr_strip_launch(const uint8_t* src, const uint64_t* offsets, uint32_t nfiles, uint64_t total, uint8_t* dst,
+                     uint64_t* new_off, void* scratch, hipStream_t s, std::string* err) {
+  const uint64_t nreg64 = prep_regions(total);
+  if (nreg64 > 0xffffffffull / kWaves) { *err = "batch too large for the CR strip"; return false; }
+  const uint32_t nreg = static_cast<uint32_t>(nreg64);
+  uint8_t* sp = static_cast<uint8_t*>(scratch);
+  uint64_t* d_total = reinterpret_cast<uint64_t*>(sp);
+  uint64_t* region_base = reinterpret_cast<uint64_t*>(sp + 64);
+  uint32_t* region_n = reinterpret_cast<uint32_t*>(sp + 64 + 8 * nreg64);
+  uint32_t* first = region_n + nreg64;
+  const uint32_t blocks = (nreg + kWaves - 1) / kWaves;
+  if (nreg) {
+    hipLaunchKernelGGL(tsg_prep_first, dim3(nfiles / 256u + 1u), dim3(256), 0, s, offsets, nfiles, nreg, first);
+    hipLaunchKernelGGL(tsg_cr_count, dim3(blocks), dim3(256), 0, s, src, total, nreg, region_n);
+  }
+  hipLaunchKernelGGL(tsg_prep_scan, dim3(1), dim3(1024), 0, s, region_n, nreg, region_base, offsets, nfiles, new_off,
+                     d_total, static_cast<uint8_t*>(nullptr), uint64_t(0));
+  if (nreg)
+    hipLaunchKernelGGL(tsg_cr_compact, dim3(blocks), dim3(256), 0, s, src, total, nreg, region_base, first, offsets,
+                       nfiles, dst, new_off);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { *err = std::string("CR strip launch: ") + hipGetErrorString(e); return false; }
+  return true;
+}
 
 size_t prep_scratch_bytes(uint64_t total, uint32_t nfiles) {
   const uint64_t nreg = prep_regions(total), nf1 = static_cast<uint64_t>(nfiles) + 1;
