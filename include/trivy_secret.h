@@ -313,6 +313,53 @@ int tsg_prepare_batch_device(tsg_engine* e, const void* d_raw, const uint64_t* r
 /* tsg_prepare_layer_tar with feed options. */
 int tsg_prepare_layer_tar_opts(const tsg_ruleset* rs, const uint8_t* tar, size_t len, const tsg_feed_opts* opts,
                                tsg_prepared** out);
+/* tsg_prepare_layer_tar_opts for a layer tar that lives in HBM (what a GPU
+ * decompressor or a peer-to-peer read delivers for an image scan): the first
+ * link of
+ *   tsg_prepare_layer_tar_device -> tsg_scan_batch_device,
+ * walker.LayerTar.Walk (pkg/fanal/walker/tar.go:35-103) included.  d_tar: len
+ * bytes on one of the engine's devices (nothing at or past len is read).
+ * The walk reads only header blocks, the payload of PAX / GNU long-name
+ * entries and the end marker, and every header passes the checksum test: one
+ * device pass tests every 512-byte block with it, marks the ones that pass
+ * and the payload blocks behind an 'x' / 'g' / 'L' / 'K' one, and stores the
+ * marked blocks into host-mapped memory; the walk then runs on the host over
+ * them, with archive/tar's semantics unchanged.  Exactness never depends on
+ * the marks: a block the walk reads that was not marked is copied from d_tar
+ * on its own -- at most two such reads of at most 512 bytes per call (the
+ * zero block of the end marker and its successor, or the block at which a
+ * malformed tar fails, or a truncated tar's partial tail); a block marked
+ * without being a header (a tar stored in the layer) only costs bytes.  The
+ * walked files pass the host gate, and the content pass of
+ * tsg_prepare_batch_device runs over the tar itself with 2n + 1 interleaved
+ * entries -- gap, file 0, gap, file 1, ..., tail gap; a gap (headers,
+ * padding, entries not handed on) is dropped -- so d_dst receives
+ * tsg_prepare_layer_tar_opts' data byte for byte, followed by 64 zero bytes.
+ * Of opts everything but `pinned` is honoured (NULL: defaults); the rule set
+ * is the engine's.  d_tar and d_dst are 16-byte aligned and do not overlap;
+ * dst_cap = len + 64 always suffices (every file follows a header block that
+ * is dropped); with less, a layer that does not fit fails as
+ * tsg_prepare_batch_device does (TSG_ERR_INVALID, the size needed in the
+ * message, d_dst untouched).  A malformed tar fails with the host call's
+ * "failed to extract the archive: ..." text and d_dst untouched; len 0, a len
+ * below 512 and zero blocks only behave as on the host.  *out: an ordinary
+ * tsg_prepared -- tsg_prepared_view gives data == NULL and the host call's
+ * offsets, index and binary, tsg_prepared_paths the "/"-prefixed paths,
+ * tsg_prepared_walk_json the same lists with "pinned": false.  *ms (may be
+ * NULL) = the content pass's kernel time.  TSG_TAR_GATHER_CAP (bytes) sets
+ * the marked blocks' first buffer capacity (default: a sixteenth of the
+ * blocks + 1024 blocks); when they do not fit the device pass is repeated
+ * with a larger buffer.  Synchronous. */
+int tsg_prepare_layer_tar_device(tsg_engine* e, const void* d_tar, uint64_t len, const tsg_feed_opts* opts,
+                                 void* d_dst, uint64_t dst_cap, tsg_prepared** out, double* ms);
+/* What the device walk of tsg_prepare_layer_tar_device took (any pointer may
+ * be NULL): whole 512-byte blocks of the tar, blocks marked, bytes that
+ * crossed the link for them, reads served from d_tar because the block was
+ * not marked (<= 2), repeats of the device pass after a full buffer, and the
+ * mark / count / scan / compact kernels' time in ms (the last repeat's).
+ * TSG_ERR_INVALID for a tsg_prepared of another call. */
+int tsg_prepared_tar_stats(const tsg_prepared* p, uint64_t* blocks, uint64_t* marked, uint64_t* gathered_bytes,
+                           uint32_t* fallback_reads, uint32_t* retries, double* scan_ms);
 /* `trivy fs` over a directory tree on disk: walker.FS.Walk (pkg/fanal/walker/
  * fs.go:25-97; filepath.WalkDir order, symlinks not followed, defaultSkipDirs
  * **\/.git proc sys dev, permission errors ignored), AnalyzeFile's gate before

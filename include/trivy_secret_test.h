@@ -152,6 +152,31 @@ int tsg_prepare_print_table(uint8_t* table);
  * compact (tools/prep_probe.py). */
 int tsg_prepared_pass_ms(const tsg_prepared* p, double* pass_ms);
 
+/* What the device walk of tsg_prepare_layer_tar_device marks (csrc/tarscan.h
+ * plan_tar_marks, the CPU statement of tarscan.hip): marks[b] = 1, b < len /
+ * 512, for every whole block that passes the header checksum test and for the
+ * payload blocks behind an 'x' / 'g' / 'L' / 'K' header with 0 <= size <= 1
+ * MiB, else 0.  Tests only. */
+int tsg_test_tar_marks(const uint8_t* tar, uint64_t len, uint8_t* marks);
+/* csrc/tarscan.h tar_block_is_header of n 512-byte blocks (is[k] = 0 / 1).  Tests only. */
+int tsg_test_tar_is_header(const uint8_t* blocks, uint64_t n, uint8_t* is);
+/* The device's mark / compact pass alone over d_tar[0, len) (16-byte aligned
+ * device memory): *n = marked blocks; when *n <= cap, idx[0..*n) their block
+ * numbers in order and blocks_out their 512 * *n bytes.  Tests only. */
+int tsg_test_tar_scan_device(tsg_engine* e, const void* d_tar, uint64_t len, uint64_t* idx, uint64_t cap, uint64_t* n,
+                             uint8_t* blocks_out);
+/* CPU model of tsg_prepare_layer_tar_device (tests without a GPU): marks ->
+ * SparseTarInput over a host copy -> walk_layer -> gate -> interleaved
+ * entries -> plan_prep.  use_marks = 0: nothing is gathered, every read of
+ * the walk is a fallback.  *fallback_reads (may be NULL) = reads not served
+ * by the marked blocks, also when the walk fails; *out: an ordinary
+ * tsg_prepared with the bytes on the host, paths and walk JSON as the device
+ * call's.  The independent restatement it is checked against is
+ * tsg_prepare_layer_tar_opts. */
+int tsg_prepare_layer_tar_device_model(const tsg_ruleset* rs, const uint8_t* tar, uint64_t len,
+                                       const tsg_feed_opts* opts, int use_marks, uint32_t* fallback_reads,
+                                       tsg_prepared** out);
+
 /* Bit of a file's flag word (engine.h kFileFoldSpecial): the file holds
  * U+0130, U+212A or U+017F, so the host scans it with the variant tables.  K1
  * may also set it for a file that shares a 16-byte word of the batch with such

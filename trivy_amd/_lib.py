@@ -213,6 +213,21 @@ SIGNATURES += [
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
     ("tsg_prepare_print_table", ctypes.c_int, [ctypes.c_void_p]),
     ("tsg_prepared_pass_ms", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    ("tsg_prepare_layer_tar_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                    ctypes.POINTER(TsgFeedOpts), ctypes.c_void_p, ctypes.c_uint64,
+                                                    ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_double)]),
+    ("tsg_prepared_tar_stats", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
+                                              ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                              ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
+                                              ctypes.POINTER(ctypes.c_double)]),
+    ("tsg_test_tar_marks", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    ("tsg_test_tar_is_header", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    ("tsg_test_tar_scan_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]),
+    ("tsg_prepare_layer_tar_device_model", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                          ctypes.POINTER(TsgFeedOpts), ctypes.c_int,
+                                                          ctypes.POINTER(ctypes.c_uint32),
+                                                          ctypes.POINTER(ctypes.c_void_p)]),
 ]
 
 # tsg_read_fn: int64_t (*)(void* user, uint8_t* buf, size_t cap)

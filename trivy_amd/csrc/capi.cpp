@@ -23,6 +23,7 @@
 #include "guard.h"
 #include "feed.h"
 #include "tar.h"
+#include "tarscan.h"
 #include "prefilter.h"
 #include "prep.h"
 #include "report.h"
@@ -76,6 +77,8 @@ struct tsg_prepared {
   std::vector<uint32_t> path_lens;
   std::string walk_json;
   double pass_ms[4] = {0, 0, 0, 0};   // tsg_prepare_batch_device: kernel time of classify, count, scan, compact
+  TarScanStats tar;                   // tsg_prepare_layer_tar_device: its device walk
+  bool has_tar = false;
 };
 
 struct tsg_result {
@@ -1381,6 +1384,21 @@ void set_scan_paths(tsg_prepared* p, const std::vector<std::string>& paths, cons
     p->path_lens.push_back(static_cast<uint32_t>(sp.size()));
   }
 }
+
+// a layer's kept "/"-prefixed paths and its walk summary
+void set_layer_walk(tsg_prepared* p, const std::vector<std::string>& paths, const LayerWalk& walk) {
+  set_scan_paths(p, paths, "/");
+  std::string& js = p->walk_json;
+  js = "{\"files\": ";
+  json_str_array(&js, paths);
+  js += ", \"opq_dirs\": ";
+  json_str_array(&js, walk.opq_dirs);
+  js += ", \"wh_files\": ";
+  json_str_array(&js, walk.wh_files);
+  js += ", \"pinned\": ";
+  js += p->b.pinned ? "true" : "false";
+  js += "}";
+}
 }  // namespace
 
 int tsg_prepare_batch_opts(const tsg_ruleset* rs, const uint8_t* raw, const uint64_t* raw_offsets, uint32_t nfiles,
@@ -1523,18 +1541,160 @@ int tsg_prepare_layer_tar_opts(const tsg_ruleset* rs, const uint8_t* tar, size_t
     delete p;
     return fail(TSG_ERR_INVALID, err);
   }
-  set_scan_paths(p, paths, "/");
-  std::string& js = p->walk_json;
-  js = "{\"files\": ";
-  json_str_array(&js, paths);
-  js += ", \"opq_dirs\": ";
-  json_str_array(&js, walk.opq_dirs);
-  js += ", \"wh_files\": ";
-  json_str_array(&js, walk.wh_files);
-  js += ", \"pinned\": ";
-  js += p->b.pinned ? "true" : "false";
-  js += "}";
+  set_layer_walk(p, paths, walk);
   *out = p;
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+namespace {
+// kinds / new starts of a walk's files (device style) -> p: kept files, "/"-prefixed paths, walk summary
+void finish_tar_device(tsg_prepared* p, const LayerWalk& walk, const std::vector<uint8_t>& kinds,
+                       const std::vector<uint64_t>& new_off) {
+  kept_from_kinds(kinds, new_off, &p->b);
+  std::vector<std::string> paths;
+  for (const TarFile& f : walk.files) paths.push_back(f.path);
+  set_layer_walk(p, paths, walk);
+  p->has_tar = true;
+}
+}  // namespace
+
+int tsg_prepare_layer_tar_device(tsg_engine* e, const void* d_tar, uint64_t len, const tsg_feed_opts* opts,
+                                 void* d_dst, uint64_t dst_cap, tsg_prepared** out, double* ms) {
+  TSG_API_TRY
+  if (!e || !out) return fail(TSG_ERR_INVALID, "NULL argument");
+  FeedOpts fo;
+  std::vector<std::string> sf, sd;
+  int nt;
+  bool pinned;
+  std::string err;
+  if (!feed_opts(opts, &fo, &sf, &sd, &nt, &pinned, &err)) return fail(TSG_ERR_INVALID, err);
+  auto p = std::make_unique<tsg_prepared>();
+  LayerWalk walk;
+  std::vector<uint8_t> kinds;
+  std::vector<uint64_t> new_off;
+  if (!e->eng->prepare_layer_tar_device(d_tar, len, fo, sf, sd, nt, d_dst, dst_cap, &walk, &kinds, &new_off, &p->tar, ms,
+                                        p->pass_ms, &err))
+    return fail(err.find("device preparation:") == 0 || err.find("failed to extract the archive:") == 0 ? TSG_ERR_INVALID
+                                                                                                        : TSG_ERR_HIP,
+                err);
+  finish_tar_device(p.get(), walk, kinds, new_off);
+  *out = p.release();
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_prepared_tar_stats(const tsg_prepared* p, uint64_t* blocks, uint64_t* marked, uint64_t* gathered_bytes,
+                           uint32_t* fallback_reads, uint32_t* retries, double* scan_ms) {
+  TSG_API_TRY
+  if (!p) return fail(TSG_ERR_INVALID, "NULL argument");
+  if (!p->has_tar) return fail(TSG_ERR_INVALID, "not a tsg_prepare_layer_tar_device result");
+  if (blocks) *blocks = p->tar.blocks;
+  if (marked) *marked = p->tar.marked;
+  if (gathered_bytes) *gathered_bytes = p->tar.gathered_bytes;
+  if (fallback_reads) *fallback_reads = p->tar.fallback_reads;
+  if (retries) *retries = p->tar.retries;
+  if (scan_ms) *scan_ms = p->tar.scan_ms;
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_test_tar_marks(const uint8_t* tar, uint64_t len, uint8_t* marks) {
+  TSG_API_TRY
+  if ((len && !tar) || (len >= kTarBlock && !marks)) return fail(TSG_ERR_INVALID, "NULL argument");
+  plan_tar_marks(tar, len, marks);
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_test_tar_is_header(const uint8_t* blocks, uint64_t n, uint8_t* is) {
+  TSG_API_TRY
+  if (n && (!blocks || !is)) return fail(TSG_ERR_INVALID, "NULL argument");
+  for (uint64_t k = 0; k < n; ++k) is[k] = tar_block_is_header(blocks + k * kTarBlock);
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_test_tar_scan_device(tsg_engine* e, const void* d_tar, uint64_t len, uint64_t* idx, uint64_t cap, uint64_t* n,
+                             uint8_t* blocks_out) {
+  TSG_API_TRY
+  if (!e || !n || (cap && (!idx || !blocks_out))) return fail(TSG_ERR_INVALID, "NULL argument");
+  std::vector<uint64_t> vi;
+  std::vector<uint8_t> vb;
+  TarScanStats st;
+  std::string err;
+  if (!e->eng->tar_scan_device(d_tar, len, &vi, &vb, &st, &err))
+    return fail(err.find("device preparation:") == 0 ? TSG_ERR_INVALID : TSG_ERR_HIP, err);
+  *n = vi.size();
+  if (vi.size() <= cap && !vi.empty()) {
+    std::memcpy(idx, vi.data(), vi.size() * 8);
+    std::memcpy(blocks_out, vb.data(), vb.size());
+  }
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_prepare_layer_tar_device_model(const tsg_ruleset* rs, const uint8_t* tar, uint64_t len,
+                                       const tsg_feed_opts* opts, int use_marks, uint32_t* fallback_reads,
+                                       tsg_prepared** out) {
+  TSG_API_TRY
+  if (!rs || !out || (len && !tar)) return fail(TSG_ERR_INVALID, "NULL argument");
+  if (fallback_reads) *fallback_reads = 0;
+  FeedOpts fo;
+  std::vector<std::string> sf, sd;
+  int nt;
+  bool pinned;
+  std::string err;
+  if (!feed_opts(opts, &fo, &sf, &sd, &nt, &pinned, &err)) return fail(TSG_ERR_INVALID, err);
+  // the device pass: marks, then the marked blocks and their numbers, compacted
+  const uint64_t nb = len / kTarBlock;
+  std::vector<uint8_t> marks(nb), blocks;
+  std::vector<uint64_t> idx;
+  if (use_marks) {
+    plan_tar_marks(tar, len, marks.data());
+    for (uint64_t b = 0; b < nb; ++b) {
+      if (!marks[b]) continue;
+      idx.push_back(b);
+      blocks.insert(blocks.end(), tar + b * kTarBlock, tar + (b + 1) * kTarBlock);
+    }
+  }
+  auto p = std::make_unique<tsg_prepared>();
+  p->tar.blocks = nb;
+  p->tar.marked = idx.size();
+  p->tar.gathered_bytes = blocks.size();
+  SparseTarInput in(idx.data(), blocks.data(), idx.size(), len,
+                    [tar, len](uint64_t off, uint8_t* dst, size_t n, std::string* e) {
+                      if (off > len || n > len - off) { *e = "internal: fallback read past the tar"; return false; }
+                      std::memcpy(dst, tar + off, n);
+                      return true;
+                    });
+  LayerWalk walk;
+  const bool walked = walk_layer(in, sf, sd, &walk, nullptr, &err);
+  if (fallback_reads) *fallback_reads = in.fallback_reads;
+  if (!walked) return fail(TSG_ERR_INVALID, err);
+  p->tar.fallback_reads = in.fallback_reads;
+  const size_t n = walk.files.size();
+  std::vector<uint64_t> cum(n + 1, 0);
+  std::vector<const char*> paths(n);
+  std::vector<uint32_t> lens(n);
+  for (size_t i = 0; i < n; ++i) {
+    cum[i + 1] = cum[i] + walk.files[i].size;
+    paths[i] = walk.files[i].path.data();
+    lens[i] = static_cast<uint32_t>(walk.files[i].path.size());
+  }
+  std::vector<uint8_t> flags(n), flags2, kinds;
+  prepare_gate(*rs->rs, fo, cum.data(), static_cast<uint32_t>(n), paths.data(), lens.data(), nt, flags.data());
+  std::vector<uint64_t> off2, new_off;
+  tar_interleave(walk.files, len, flags.data(), &off2, &flags2);
+  PrepPlan plan;
+  plan_prep(tar, off2.data(), static_cast<uint32_t>(2 * n + 1), flags2.data(), &plan);
+  tar_uninterleave(plan.kinds, plan.new_off, &kinds, &new_off);
+  finish_tar_device(p.get(), walk, kinds, new_off);
+  const size_t m = plan.out.size();
+  p->b.data = std::shared_ptr<uint8_t>(new uint8_t[m + 64], std::default_delete<uint8_t[]>());
+  if (m) std::memcpy(p->b.data.get(), plan.out.data(), m);
+  std::memset(p->b.data.get() + m, 0, 64);
+  *out = p.release();
   return TSG_OK;
   TSG_API_CATCH
 }

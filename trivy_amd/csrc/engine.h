@@ -23,6 +23,10 @@
 
 namespace tsg {
 
+struct FeedOpts;       // feed.h
+struct LayerWalk;      // tar.h
+struct TarScanStats;   // tarscan.h
+
 struct ScanStats {
   double k1_ms = 0, k2_ms = 0, h2d_ms = 0, d2h_ms = 0, host_ms = 0, total_ms = 0;
   double gpu_wall_ms = 0;               // sum over devices of the driver threads' busy time
@@ -152,6 +156,27 @@ class Engine {
                       uint64_t dst_cap, uint64_t* h_new_off, uint8_t* h_kinds, uint64_t* out_total, double* ms,
                       double* pass_ms, std::string* err);
 
+  // The mark / compact pass of the device tar walk alone (tarscan.hip; test
+  // hook): the block numbers plan_tar_marks marks in d_tar[0, len), in order,
+  // and those blocks' bytes.
+  bool tar_scan_device(const void* d_tar, uint64_t len, std::vector<uint64_t>* idx, std::vector<uint8_t>* blocks,
+                       TarScanStats* st, std::string* err);
+
+  // walker.LayerTar.Walk plus the content preparation of a layer tar in
+  // device memory: the blocks walk_layer may read are marked and gathered on
+  // the device (tarscan.h), the walk runs on the host over them
+  // (SparseTarInput; a read they miss is a small copy from d_tar), the walked
+  // files pass prepare_gate, and prepare_device takes the tar itself with
+  // 2n + 1 interleaved entries (gap, file, gap, ..., tail gap; gaps dropped).
+  // kinds / new_off: of the walk's n files.  A malformed tar fails with
+  // walk_layer's text before d_dst is touched; pointer checks, capacity
+  // failure and times are prepare_device's.
+  bool prepare_layer_tar_device(const void* d_tar, uint64_t len, const FeedOpts& fo,
+                                const std::vector<std::string>& skip_files, const std::vector<std::string>& skip_dirs,
+                                int threads, void* d_dst, uint64_t dst_cap, LayerWalk* walk, std::vector<uint8_t>* kinds,
+                                std::vector<uint64_t>* new_off, TarScanStats* st, double* ms, double* pass_ms,
+                                std::string* err);
+
   // Lanes created over all devices, call contexts, and confirm-pool threads
   // started (test hook: the per-file queue's footprint).
   void footprint(uint32_t* lanes, uint32_t* calls, uint32_t* pool_threads);
@@ -218,6 +243,8 @@ class Engine {
                        uint64_t* nfind, bool gpu_in_flight);
   Lane* acquire_lane(DeviceTables& dt, std::string* err);
   void release_lane(DeviceTables& dt, Lane* ln);
+  bool tar_gather(DeviceTables& dt, Lane* ln, const uint8_t* d_tar, uint64_t len, uint64_t* cap_blocks,
+                  TarScanStats* st, std::string* err);
   DeviceTables* tables_of(int device);                   // NULL: not one of the engine's devices
   CallCtx* acquire_call();
   void release_call(CallCtx* cc);
@@ -289,6 +316,7 @@ class Engine {
   std::atomic<bool> keep_raw_{false};
   std::atomic<bool> keep_gather_{false};
   uint64_t cand_cap0_ = 0;              // a fresh lane's candidate capacity (TSG_CAND_CAP); 0 = the lane's default
+  uint64_t tar_gather_cap_ = 0;         // the device tar walk's first gather capacity in bytes (TSG_TAR_GATHER_CAP); 0 = 1/16 of the blocks + 1024
   uint64_t gather_cap_ = 0;             // a gather buffer's first capacity in bytes (TSG_GATHER_CAP); 0 = bytes / 8 + 1 MiB
   std::mutex k2s_mu_;
   std::vector<unsigned long long> k2s_;  // 4 per rule: hits, past the keyword gate, verify starts, bytes walked

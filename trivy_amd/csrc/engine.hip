@@ -1669,6 +1669,10 @@ struct Lane : LaneStreams {
   DevBuf<unsigned int> d_cnt;
   DevBuf<uint8_t> d_cr;                // CR strip scratch (crstrip.h)
   DevBuf<uint8_t> d_prep;              // raw-batch preparation scratch (prep.hip)
+  // device tar walk (tarscan.hip): its scratch, and the marked blocks with
+  // their block numbers behind them, in host-mapped memory the kernel stores into
+  DevBuf<uint8_t> d_tarscan;
+  PinnedBuf tar_out;
   // device-only scans (gather.hip): per-file need flags and gather offsets,
   // the run table, [runs, gather_total]; their readbacks; the gather buffer
   // size the lane's last segment ended with
@@ -2069,6 +2073,7 @@ std::unique_ptr<Engine> Engine::create(std::shared_ptr<const Ruleset> rs, const 
   }
   if (e->host_profile_) g_scan_prof_on.store(true, std::memory_order_relaxed);
   env_int("TSG_GATHER_CAP", 256, INT64_MAX, &e->gather_cap_);   // (from 256 bytes: tests force the capacity retry)
+  env_int("TSG_TAR_GATHER_CAP", 1, INT64_MAX, &e->tar_gather_cap_);   // (tests force the capacity retry)
   env_int("TSG_CAND_CAP", 16, INT64_MAX, &e->cand_cap0_);       // (tests force K2's candidate-overflow retry on small batches)
   env_int("TSG_K1_TAIL_ROUNDS", 0, 16, &e->k1_tail_rounds_);
   if (const char* c = std::getenv("TSG_K1_TOP8")) e->k1_top8_ = std::max(0, std::min(2, std::atoi(c)));
@@ -3365,6 +3370,9 @@ bool Engine::strip_cr(const void* d_src, const uint64_t* d_off, uint32_t nfiles,
 
 }  // namespace tsg
 #include "prep_dev.h"   // (this file's include block belongs to K1's build hash)
+#include "feed.h"
+#include "tar.h"
+#include "tarscan_dev.h"
 namespace tsg {
 
 bool Engine::prepare_device(const void* d_raw, const uint64_t* h_off, uint32_t nfiles, const uint8_t* h_flags,
@@ -3437,6 +3445,146 @@ bool Engine::prepare_device(const void* d_raw, const uint64_t* h_off, uint32_t n
   }
   if (ms) *ms = pm[0] + pm[1] + pm[2] + pm[3];
   if (pass_ms) for (int i = 0; i < 4; ++i) pass_ms[i] = pm[i];
+  return true;
+}
+
+// The mark / compact pass on lane ln (tarscan.hip), repeated with a larger
+// buffer while the marked blocks do not fit.  After it ln->tar_out holds
+// st->marked blocks of 512 bytes and, from byte *cap_blocks * 512 on, their
+// block numbers.
+bool Engine::tar_gather(DeviceTables& dt, Lane* ln, const uint8_t* d_tar, uint64_t len, uint64_t* cap_blocks,
+                        TarScanStats* st, std::string* err) {
+  (void)dt;
+  const uint64_t nblocks = len / kTarBlock, entry = kTarBlock + sizeof(uint64_t);
+  st->blocks = nblocks;
+  uint64_t cap = tar_gather_cap_ ? tar_gather_cap_ / entry : nblocks / 16 + 1024;
+  cap = std::min(cap, nblocks);
+  *cap_blocks = cap;
+  if (nblocks == 0) return true;
+  if (!ln->d_tarscan.ensure(tar_scan_scratch_bytes(len), err)) return false;
+  const TarScanScratch sc = tar_scan_scratch_layout(ln->d_tarscan.p, len);
+  for (;;) {
+    *cap_blocks = cap;
+    if (!ln->tar_out.ensure(cap * entry, hipHostMallocMapped | hipHostMallocCoherent, err, 64)) return false;
+    uint8_t* out = static_cast<uint8_t*>(ln->tar_out.d);
+    uint64_t marked = 0;
+    bool ok = hipEventRecord(ln->ev[0], ln->compute) == hipSuccess &&
+              tar_scan_launch(d_tar, len, sc, out, reinterpret_cast<uint64_t*>(out + cap * kTarBlock), cap, ln->compute, err) &&
+              hipEventRecord(ln->ev[1], ln->compute) == hipSuccess &&
+              hipMemcpyAsync(&marked, sc.total, 8, hipMemcpyDeviceToHost, ln->compute) == hipSuccess &&
+              hipStreamSynchronize(ln->compute) == hipSuccess;
+    float f = 0;
+    ok = ok && hipEventElapsedTime(&f, ln->ev[0], ln->ev[1]) == hipSuccess;
+    if (!ok) {
+      if (err->empty()) *err = "device tar walk failed on the device";
+      return false;
+    }
+    st->scan_ms = f;
+    st->marked = marked;
+    st->gathered_bytes = marked * kTarBlock;
+    if (marked <= cap) return true;
+    if (marked > nblocks) { *err = "device tar walk: inconsistent mark count"; return false; }
+    ++st->retries;
+    cap = marked;
+  }
+}
+
+namespace {
+// prepare_device's pointer checks for a source of `total` bytes and a
+// destination of dst_cap (d_dst NULL with dst_cap 0: a source alone)
+bool check_device_pair(const void* d_raw, uint64_t total, const void* d_dst, uint64_t dst_cap, std::string* err) {
+  if ((total && !d_raw) || (dst_cap && !d_dst)) { *err = "device preparation: null buffer"; return false; }
+  if ((reinterpret_cast<uintptr_t>(d_raw) | reinterpret_cast<uintptr_t>(d_dst)) & 15u) {
+    *err = "device preparation: buffers must be 16-byte aligned";
+    return false;
+  }
+  const uintptr_t ra = reinterpret_cast<uintptr_t>(d_raw), da = reinterpret_cast<uintptr_t>(d_dst);
+  if (total && dst_cap && ra < da + dst_cap && da < ra + total) {
+    *err = "device preparation: d_raw and d_dst must not overlap";
+    return false;
+  }
+  return true;
+}
+}  // namespace
+
+bool Engine::tar_scan_device(const void* d_tar, uint64_t len, std::vector<uint64_t>* idx, std::vector<uint8_t>* blocks,
+                             TarScanStats* st, std::string* err) {
+  if (!check_device_pair(d_tar, len, nullptr, 0, err)) return false;
+  DeviceTables* dtp = tables_of(len ? device_of(d_tar) : dev_[0]->device);
+  if (!dtp) { *err = "device preparation: buffers must be device memory of one of the engine's devices"; return false; }
+  Lane* ln = acquire_lane(*dtp, err);
+  if (!ln) return false;
+  uint64_t cap = 0;
+  const bool ok = hipSetDevice(dtp->device) == hipSuccess &&
+                  tar_gather(*dtp, ln, static_cast<const uint8_t*>(d_tar), len, &cap, st, err);
+  if (ok) {
+    const uint8_t* h = ln->tar_out.as<uint8_t>();
+    const uint64_t* hi = reinterpret_cast<const uint64_t*>(h + cap * kTarBlock);
+    idx->assign(hi, hi + st->marked);
+    blocks->assign(h, h + st->marked * kTarBlock);
+  }
+  release_lane(*dtp, ln);
+  if (!ok && err->empty()) *err = "device tar walk failed on the device";
+  return ok;
+}
+
+bool Engine::prepare_layer_tar_device(const void* d_tar, uint64_t len, const FeedOpts& fo,
+                                      const std::vector<std::string>& skip_files,
+                                      const std::vector<std::string>& skip_dirs, int threads, void* d_dst,
+                                      uint64_t dst_cap, LayerWalk* walk, std::vector<uint8_t>* kinds,
+                                      std::vector<uint64_t>* new_off, TarScanStats* st, double* ms, double* pass_ms,
+                                      std::string* err) {
+  if (!check_device_pair(d_tar, len, d_dst, dst_cap, err)) return false;
+  const int dev = len ? device_of(d_tar) : dst_cap ? device_of(d_dst) : dev_[0]->device;
+  DeviceTables* dtp = tables_of(dev);
+  if (!dtp || (dst_cap && device_of(d_dst) != dev)) {
+    *err = "device preparation: buffers must be device memory of one of the engine's devices";
+    return false;
+  }
+  DeviceTables& dt = *dtp;
+  Lane* ln = acquire_lane(dt, err);
+  if (!ln) return false;
+  const uint8_t* tar = static_cast<const uint8_t*>(d_tar);
+  uint64_t cap = 0;
+  bool ok = hipSetDevice(dt.device) == hipSuccess && tar_gather(dt, ln, tar, len, &cap, st, err);
+  if (ok) {
+    // the walk, on the host over the gathered blocks; what they miss is read from the device
+    const uint8_t* h = ln->tar_out.as<uint8_t>();
+    hipStream_t s = ln->compute;
+    SparseTarInput in(reinterpret_cast<const uint64_t*>(h + cap * kTarBlock), h, static_cast<size_t>(st->marked), len,
+                      [tar, s](uint64_t off, uint8_t* dst, size_t n, std::string* e) {
+                        if (hipMemcpyAsync(dst, tar + off, n, hipMemcpyDeviceToHost, s) == hipSuccess &&
+                            hipStreamSynchronize(s) == hipSuccess)
+                          return true;
+                        *e = "device tar walk: reading the tar failed";
+                        return false;
+                      });
+    ok = walk_layer(in, skip_files, skip_dirs, walk, nullptr, err);
+    st->fallback_reads = in.fallback_reads;
+  }
+  release_lane(dt, ln);
+  if (!ok) {
+    if (err->empty()) *err = "device tar walk failed on the device";
+    return false;
+  }
+  const size_t n = walk->files.size();
+  if (n > 0x7fffffffu) { *err = "device preparation: too many files in the layer"; return false; }
+  std::vector<uint64_t> cum(n + 1, 0);
+  std::vector<const char*> paths(n);
+  std::vector<uint32_t> lens(n);
+  for (size_t i = 0; i < n; ++i) {
+    cum[i + 1] = cum[i] + walk->files[i].size;
+    paths[i] = walk->files[i].path.data();
+    lens[i] = static_cast<uint32_t>(walk->files[i].path.size());
+  }
+  std::vector<uint8_t> flags(n), flags2, kinds2(2 * n + 1);
+  prepare_gate(*rs_, fo, cum.data(), static_cast<uint32_t>(n), paths.data(), lens.data(), threads, flags.data());
+  std::vector<uint64_t> off2, new_off2(2 * n + 2);
+  tar_interleave(walk->files, len, flags.data(), &off2, &flags2);
+  if (!prepare_device(d_tar, off2.data(), static_cast<uint32_t>(2 * n + 1), flags2.data(), d_dst, dst_cap, new_off2.data(),
+                      kinds2.data(), nullptr, ms, pass_ms, err))
+    return false;
+  tar_uninterleave(kinds2, new_off2, kinds, new_off);
   return true;
 }
 

@@ -561,6 +561,12 @@ bool cr_strip_launch(const uint8_t* src, const uint64_t* offsets, uint32_t nfile
   return true;
 }
 
+void region_scan_launch(const uint32_t* region_n, uint32_t nregions, uint64_t* region_base, uint64_t* total,
+                        uint64_t* pad, hipStream_t s) {
+  hipLaunchKernelGGL(tsg_prep_scan, dim3(1), dim3(1024), 0, s, region_n, nregions, region_base, pad, 0u, pad + 1, total,
+                     static_cast<uint8_t*>(nullptr), uint64_t(0));
+}
+
 size_t prep_scratch_bytes(uint64_t total, uint32_t nfiles) {
   const uint64_t nreg = prep_regions(total), nf1 = static_cast<uint64_t>(nfiles) + 1;
   return 128 + align64(nf1 * 8) * 2 + align64(nreg * 8) + align64(nreg * 4) * 2 + align64(nfiles) * 2 + 64;

@@ -35,4 +35,11 @@ PrepScratch prep_scratch_layout(void* scratch, uint64_t total, uint32_t nfiles);
 bool prep_launch(const uint8_t* src, uint64_t total, uint32_t nfiles, uint8_t* dst, uint64_t dst_cap,
                  const PrepScratch& sc, hipStream_t s, hipEvent_t* pass_ev, std::string* err);
 
+// The skeleton's middle pass for another compaction (tarscan.hip): region_base[r]
+// = region_n[0] + ... + region_n[r - 1], *total = the sum.  pad: two device
+// words, pad[0] = 0 (the scan takes them as an empty batch's offsets and new
+// starts and sets pad[1] = 0).
+void region_scan_launch(const uint32_t* region_n, uint32_t nregions, uint64_t* region_base, uint64_t* total,
+                        uint64_t* pad, hipStream_t s);
+
 }  // namespace tsg

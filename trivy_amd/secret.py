@@ -228,6 +228,73 @@ class Scanner:
         out = (dst, offs, scan_paths, idx, binf, ms.value)
         return out + (list(passes),) if with_passes else out
 
+    def PrepareLayerTarDevice(self, d_tar, length=None, skip_files=(), skip_dirs=(), file_patterns=(), config_path="",
+                              threads=0, dst_cap=None, with_stats=False):
+        """One container layer whose uncompressed tar lives in HBM
+        (tsg_prepare_layer_tar_device): walker.LayerTar.Walk
+        (pkg/fanal/walker/tar.go:35-103) and the analyzer's content preparation
+        without the tar crossing the link -- the device twin of PrepareLayerTar.
+
+        d_tar: uint8 device tensor (16-byte aligned), of which the first
+        `length` bytes (default: all) are the tar.  The GPU marks the blocks
+        the walk may read (headers by their checksum, PAX / GNU long-name
+        payloads) and stores them into host-mapped memory; the walk runs on the
+        host over them; the content pass then packs the kept files' prepared
+        contents into a new tensor of length + 64 bytes (dst_cap: another size,
+        for tests).
+
+        Returns (d_dst, offsets, scan_paths, binary, walk, kernel_ms): offsets
+        (nkept + 1, uint64) cut d_dst, scan_paths are the "/"-prefixed image
+        paths, walk the dict PrepareLayerTar returns.  with_stats appends a
+        dict of the device walk (blocks, marked, gathered_bytes,
+        fallback_reads, retries, scan_ms, pass_ms).  Raises WalkError on a
+        malformed tar.  The scan to follow is
+        ScanBatchDevice(d_dst, offsets, scan_paths, binary)."""
+        import torch
+        L = _lib.lib()
+        if d_tar.dtype != torch.uint8 or not d_tar.is_cuda or not d_tar.is_contiguous():
+            raise ValueError("d_tar must be a contiguous uint8 device tensor")
+        n = d_tar.numel() if length is None else int(length)
+        if n < 0 or n > d_tar.numel():
+            raise ValueError("length is past the end of d_tar")
+        if d_tar.data_ptr() & 15:
+            raise ValueError("d_tar must be 16-byte aligned")
+        if dst_cap is None:
+            dst_cap = n + 64
+        dst = torch.empty(max(int(dst_cap), 16), dtype=torch.uint8, device=d_tar.device)
+        o, keep = _lib.feed_opts(config_path, file_patterns, skip_files, skip_dirs, threads=threads)
+        torch.cuda.current_stream(d_tar.device).synchronize()     # the engine runs on its own stream
+        h, ms = ctypes.c_void_p(), ctypes.c_double()
+        rc = L.tsg_prepare_layer_tar_device(self.engine(), ctypes.c_void_p(d_tar.data_ptr()), n, ctypes.byref(o),
+                                            ctypes.c_void_p(dst.data_ptr()), int(dst_cap), ctypes.byref(h),
+                                            ctypes.byref(ms))
+        del keep
+        if rc != 0:
+            msg = L.tsg_last_error().decode("utf-8", "replace")
+            if msg.startswith("failed to extract the archive:"):
+                raise WalkError(msg)
+            _lib.check(rc)
+        try:
+            offs, _idx, binf, _data = _prepared_view(L, h)
+            walk = json.loads(L.tsg_prepared_walk_json(h).decode("utf-8", "surrogateescape"))
+            pp, pl = ctypes.POINTER(ctypes.c_char_p)(), ctypes.POINTER(ctypes.c_uint32)()
+            _lib.check(L.tsg_prepared_paths(h, ctypes.byref(pp), ctypes.byref(pl)))
+            scan_paths = [ctypes.string_at(pp[k], pl[k]).decode("utf-8", "surrogateescape") for k in range(len(binf))]
+            out = (dst, offs, scan_paths, binf, walk, ms.value)
+            if not with_stats:
+                return out
+            blocks, marked, gbytes = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+            fb, retries, scan_ms = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_double()
+            _lib.check(L.tsg_prepared_tar_stats(h, ctypes.byref(blocks), ctypes.byref(marked), ctypes.byref(gbytes),
+                                                ctypes.byref(fb), ctypes.byref(retries), ctypes.byref(scan_ms)))
+            passes = (ctypes.c_double * 4)()
+            _lib.check(L.tsg_prepared_pass_ms(h, passes))
+            return out + ({"blocks": blocks.value, "marked": marked.value, "gathered_bytes": gbytes.value,
+                           "fallback_reads": fb.value, "retries": retries.value, "scan_ms": scan_ms.value,
+                           "pass_ms": list(passes)},)
+        finally:
+            L.tsg_prepared_free(h)
+
     def Scan(self, args):
         return self.ScanBatch([args])[0]
 
