@@ -96,11 +96,17 @@ typedef struct tsg_stats {
   uint32_t k1_launches; /* K1 launches (segments x scan-DFA groups) */
   uint32_t devices;     /* devices that took part */
   double feed_ms;       /* uploaded batches: wall time until the last segment's upload had landed */
-  /* wire packing of uploaded batches (ASCII blocks cross the link as 7 bits per byte) */
+  /* wire packing of uploaded batches (text blocks cross the link as 6 or 7 bits per byte) */
   uint64_t wire_bytes;    /* bytes of the batch's data that crossed the link (bytes when nothing went packed) */
   uint32_t packed_strips; /* strips sent packed */
   uint32_t raw_strips;    /* strips sent as they are by the strip feeder */
   double pack_ms;         /* the packer threads' summed busy time */
+  /* blocks (4096 bytes) of the strips sent packed, by the mode they crossed in, and the bytes the 6-bit
+   * blocks escaped (the 7-bit codec has no 6-bit blocks) */
+  uint64_t blocks_6bit;
+  uint64_t blocks_7bit;
+  uint64_t blocks_raw;
+  uint64_t escaped_bytes;
 } tsg_stats;
 
 const char* tsg_last_error(void);

@@ -302,6 +302,17 @@ int tsg_test_wire_pack(const uint8_t* src, size_t n, int path, uint8_t* packed, 
  * past them.  Never used by tsg_scan_batch. */
 int tsg_test_wire_unpack_device(const uint8_t* packed, size_t packed_len, const uint32_t* table, size_t n,
                                 uint8_t* out);
+/* The same two hooks for the 6-bit codec with escapes (csrc/wirepack.h, "v2").
+ * path 0: the CPU's best, 1: scalar, 2: AVX2, 3: AVX-512 VBMI (the best path
+ * below it on a CPU without the one asked for; *path_used tells which ran).
+ * packed: n + 16 bytes always suffice.  table: one entry per block, bit 31 set
+ * for a raw block, bit 30 for a 6-bit one.  alpha: the strip's alphabets, 64
+ * bytes per 64 KiB region rounded up to a multiple of 256 bytes in all.
+ * counts (4 values, may be NULL): 6-bit, 7-bit and raw blocks, escaped bytes. */
+int tsg_test_wire_pack2(const uint8_t* src, size_t n, int path, uint8_t* packed, size_t packed_cap, uint32_t* table,
+                        uint8_t* alpha, size_t* packed_len, int* path_used, uint64_t* counts, uint8_t* back);
+int tsg_test_wire_unpack2_device(const uint8_t* packed, size_t packed_len, const uint32_t* table, const uint8_t* alpha,
+                                 size_t n, uint8_t* out);
 
 /* The same two pipelines with the CPU model of the GPU passes as the scan
  * stage (tsg_scan_table_model's); tests only, never the product path. */

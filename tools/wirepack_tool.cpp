@@ -8,10 +8,17 @@
 //   g++ -O3 -std=c++17 -march=x86-64-v2 -I trivy_amd/csrc tools/wirepack_tool.cpp trivy_amd/csrc/wirepack.cpp \
 //       -o tools/wirepack_tool -lpthread
 //   tools/wirepack_tool rate [MiB per thread] [threads ...]   # pack GB/s of input against memcpy
+//   tools/wirepack_tool_asan check2      # the 6-bit codec (v2): the cases of tests/test_wirepack2.py
+//   tools/wirepack_tool rate2 FILE [MiB per thread] [threads ...]
+//       # v2 on FILE's bytes (repeated to fill 64 MiB strips): GB/s of input, packed / input with the strips'
+//       # heads, escaped share, blocks per mode, beside the 7-bit packer on the same bytes
+//       # (WIREPACK_PATH=1|2|3 in the environment: the scalar, AVX2 or VBMI path instead of the CPU's best)
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <memory>
 #include <thread>
 #include <vector>
@@ -133,9 +140,183 @@ static int rate(int argc, char** argv) {
   return 0;
 }
 
+// ---- v2
+
+static const char* path_name(int p) { return p == kWireVbmi ? "vbmi" : p == kWireAvx2 ? "avx2" : "scalar"; }
+
+// as one_case: every path from an exact-size source into exact-size buffers, the round trip from exact-size
+// packed bytes, and the format's invariants; the exact bytes are the Python model's to predict
+static void one_case2(const char* name, const std::vector<uint8_t>& data, size_t mis) {
+  const size_t n = data.size();
+  std::unique_ptr<uint8_t[]> raw(new uint8_t[n + mis]);
+  uint8_t* src = raw.get() + mis;
+  if (n) std::memcpy(src, data.data(), n);
+  std::vector<uint8_t> packed[3], alpha[3];
+  std::vector<uint32_t> tab[3];
+  for (int k = 0; k < 3; ++k) {
+    std::unique_ptr<uint8_t[]> dst(new uint8_t[wire2_bound(n)]);
+    tab[k].assign(wire_blocks(n), 0);
+    alpha[k].assign(wire2_alpha_bytes(n), 0xEE);
+    Wire2Stats st;
+    const size_t pl = wire_pack2(src, n, dst.get(), tab[k].data(), alpha[k].data(), k + 1, &st);
+    packed[k].assign(dst.get(), dst.get() + pl);
+    std::unique_ptr<uint8_t[]> back(new uint8_t[n]);
+    wire_unpack2(packed[k].data(), tab[k].data(), alpha[k].data(), n, back.get());
+    if (n && std::memcmp(back.get(), src, n) != 0) { std::printf("FAIL %s: round trip (path %d)\n", name, k + 1); ++g_fail; }
+    if (pl > n + 15) { std::printf("FAIL %s: packed size %zu (path %d)\n", name, pl, k + 1); ++g_fail; }
+    if (st.blocks6 + st.blocks7 + st.blocks_raw != wire_blocks(n)) { std::printf("FAIL %s: block counts\n", name); ++g_fail; }
+    for (uint32_t t : tab[k])
+      if ((t & 15u) || ((t & kWireRawBit) && (t & kWire6Bit))) { std::printf("FAIL %s: table entry %08x\n", name, t); ++g_fail; }
+  }
+  for (int k = 1; k < 3; ++k)
+    if (packed[0] != packed[k] || tab[0] != tab[k] || alpha[0] != alpha[k]) {
+      std::printf("FAIL %s: path %d differs from the scalar path\n", name, k + 1);
+      ++g_fail;
+    }
+}
+
+static std::vector<uint8_t> words(size_t n, uint32_t seed) {
+  static const char vals[] = "abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789 ";   // 63 values
+  std::vector<uint8_t> v(n);
+  for (size_t i = 0; i < n; ++i) {
+    seed = seed * 1664525u + 1013904223u;
+    v[i] = static_cast<uint8_t>(vals[i % kWire2Sample == 0 ? i / kWire2Sample % 63 : (seed >> 16) % 63]);
+  }
+  return v;
+}
+
+static int check2() {
+  const size_t B = kWireBlock, R = kWire2Region;
+  const size_t lens[] = {0, 1, 3, 4, 5, 15, 16, 17, 63, 64, 65, B - 1, B, B + 1, 2 * B + 5};
+  char name[64];
+  for (size_t n : lens)
+    for (size_t mis : {size_t(0), size_t(1), size_t(3), size_t(13)}) {
+      std::snprintf(name, sizeof name, "words len %zu mis %zu", n, mis);
+      one_case2(name, words(n, 7 + static_cast<uint32_t>(n)), mis);
+      std::snprintf(name, sizeof name, "noise len %zu mis %zu", n, mis);
+      one_case2(name, text(n, 9 + static_cast<uint32_t>(n)), mis);
+    }
+  const uint8_t vals[] = {0x00, 0x7F, 0x80, 0xFF};
+  const size_t strip = R + 4 * B;
+  for (uint8_t v : vals)
+    for (size_t pos : {size_t(0), B - 1, B, R - 1, R, strip - 1}) {
+      std::vector<uint8_t> d = words(strip, 99);
+      d[pos] = v;
+      std::snprintf(name, sizeof name, "value %02x at %zu", v, pos);
+      one_case2(name, d, 1);
+    }
+  // escape counts around the points where 7-bit and raw take over, and far past them
+  for (size_t k : {size_t(1), size_t(495), size_t(496), size_t(497), size_t(1008), size_t(1009), size_t(2048), size_t(4096)})
+    for (uint8_t v : {uint8_t('#'), uint8_t(0x80)}) {
+      std::vector<uint8_t> d = words(B, 5);
+      for (size_t i = 0; i < k; ++i) d[i * (B / k) + (k < B / 2 ? 1 : 0)] = v;
+      std::snprintf(name, sizeof name, "%zu escapes of %02x", k, v);
+      one_case2(name, d, 3);
+    }
+  for (size_t tail : {size_t(1), size_t(2), size_t(3)}) {
+    std::vector<uint8_t> d = words(3 * B + 1028 + tail, 3);
+    for (size_t i = d.size() - tail; i < d.size(); ++i) d[i] = '@';
+    std::snprintf(name, sizeof name, "escapes in a last group of %zu", tail);
+    one_case2(name, d, 13);
+  }
+  {
+    std::vector<uint8_t> d(3 * B + 18);
+    for (size_t i = 0; i < d.size(); ++i) d[i] = i % 2 ? 0xA9 : 0xC3;
+    one_case2("all non-ASCII", d, 0);
+  }
+  {
+    std::vector<uint8_t> d = words(10 * B, 11), x = text(B, 12), y = words(B + 100, 13);
+    d.insert(d.end(), x.begin(), x.end());
+    d.insert(d.end(), B, 0xC3);
+    d.insert(d.end(), y.begin(), y.end());
+    one_case2("three modes", d, 1);
+  }
+  {
+    std::vector<uint8_t> d = words(R, 21), x = text(R / 2 + 7, 22);
+    for (uint8_t& c : x) c = static_cast<uint8_t>('!' + c % 15);
+    d.insert(d.end(), x.begin(), x.end());
+    one_case2("two regions", d, 3);
+  }
+  std::printf("wirepack check2: %s (AVX2 %s, VBMI %s)\n", g_fail ? "FAILED" : "ok",
+              wire_have_avx2() ? "yes" : "no: scalar in its place", wire_have_vbmi() ? "yes" : "no: the path below in its place");
+  return g_fail ? 1 : 0;
+}
+
+static int rate2(int argc, char** argv) {
+  if (argc < 3) return 2;
+  std::ifstream f(argv[2], std::ios::binary);
+  std::vector<uint8_t> file((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+  if (file.empty()) { std::fprintf(stderr, "cannot read %s\n", argv[2]); return 2; }
+  const size_t bytes = static_cast<size_t>(argc > 3 ? std::atoi(argv[3]) : 64) << 20;
+  std::vector<int> counts;
+  for (int i = 4; i < argc; ++i) counts.push_back(std::atoi(argv[i]));
+  if (counts.empty()) counts = {1, 8, 14, 16};
+  int maxt = 1;
+  for (int c : counts) maxt = c > maxt ? c : maxt;
+  // thread t packs `bytes` of the file from its own offset (wrapping), as one strip
+  std::vector<std::vector<uint8_t>> src(maxt), dst(maxt);
+  for (int t = 0; t < maxt; ++t) {
+    src[t].resize(bytes);
+    size_t at = (file.size() / maxt * t) % file.size();
+    for (size_t o = 0; o < bytes;) {
+      const size_t k = std::min(bytes - o, file.size() - at);
+      std::memcpy(src[t].data() + o, file.data() + at, k);
+      o += k;
+      at = 0;
+    }
+    dst[t].assign(wire2_bound(bytes), 1);
+  }
+  const int reps = 4;
+  // WIREPACK_PATH=1|2|3: the scalar, AVX2 or VBMI path instead of the CPU's best
+  const int path = std::getenv("WIREPACK_PATH") ? std::atoi(std::getenv("WIREPACK_PATH")) : kWireAuto;
+  for (int nt : counts) {
+    if (nt < 1) continue;
+    double gbps[2] = {0, 0};
+    std::vector<Wire2Stats> st(nt);
+    std::vector<size_t> pl2(nt), pl1(nt);
+    for (int v2 = 1; v2 >= 0; --v2)
+      for (int pass = 0; pass < 2; ++pass) {     // (the first pass warms)
+        auto t0 = std::chrono::steady_clock::now();
+        std::vector<std::thread> th;
+        for (int t = 0; t < nt; ++t)
+          th.emplace_back([&, t] {
+            std::vector<uint32_t> tab(wire_blocks(bytes));
+            std::vector<uint8_t> alpha(wire2_alpha_bytes(bytes));
+            for (int r = 0; r < reps; ++r) {
+              if (v2) pl2[t] = wire_pack2(src[t].data(), bytes, dst[t].data(), tab.data(), alpha.data(), path, &st[t]);
+              else pl1[t] = wire_pack(src[t].data(), bytes, dst[t].data(), tab.data(), kWireAuto);
+            }
+          });
+        for (auto& x : th) x.join();
+        const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        gbps[v2] = static_cast<double>(bytes) * nt * reps / s / 1e9;
+      }
+    Wire2Stats a;
+    double sent2 = 0, sent1 = 0;
+    for (int t = 0; t < nt; ++t) {
+      a.blocks6 += st[t].blocks6; a.blocks7 += st[t].blocks7; a.blocks_raw += st[t].blocks_raw; a.escaped += st[t].escaped;
+      sent2 += static_cast<double>(wire_table_bytes(bytes) + wire2_alpha_bytes(bytes) + pl2[t]);
+      sent1 += static_cast<double>(wire_table_bytes(bytes) + pl1[t]);
+    }
+    const double in = static_cast<double>(bytes) * nt;
+    std::printf("{\"file\": \"%s\", \"file_mb\": %.1f, \"threads\": %d, \"mib_per_thread\": %zu, \"path\": \"%s\", "
+                "\"pack2_gbps\": %.2f, \"ratio2\": %.4f, \"escaped_share\": %.5f, \"blocks_6bit\": %llu, "
+                "\"blocks_7bit\": %llu, \"blocks_raw\": %llu, \"pack7_gbps\": %.2f, \"ratio7\": %.4f}\n",
+                argv[2], file.size() / 1e6, nt, bytes >> 20, path_name(wire2_path(path)), gbps[1], sent2 / in,
+                static_cast<double>(a.escaped) / in, static_cast<unsigned long long>(a.blocks6),
+                static_cast<unsigned long long>(a.blocks7), static_cast<unsigned long long>(a.blocks_raw), gbps[0],
+                sent1 / in);
+    std::fflush(stdout);
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc > 1 && std::strcmp(argv[1], "check") == 0) return check();
   if (argc > 1 && std::strcmp(argv[1], "rate") == 0) return rate(argc, argv);
-  std::fprintf(stderr, "usage: %s check | rate [MiB per thread] [threads ...]\n", argv[0]);
+  if (argc > 1 && std::strcmp(argv[1], "check2") == 0) return check2();
+  if (argc > 2 && std::strcmp(argv[1], "rate2") == 0) return rate2(argc, argv);
+  std::fprintf(stderr, "usage: %s check | rate [MiB per thread] [threads ...] | check2 | rate2 FILE [MiB per thread] "
+                       "[threads ...]\n", argv[0]);
   return 2;
 }

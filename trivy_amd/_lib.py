@@ -61,7 +61,9 @@ class TsgStats(ctypes.Structure):
                 ("pieces", ctypes.c_uint32), ("k1_launches", ctypes.c_uint32), ("devices", ctypes.c_uint32),
                 ("feed_ms", ctypes.c_double),
                 ("wire_bytes", ctypes.c_uint64), ("packed_strips", ctypes.c_uint32), ("raw_strips", ctypes.c_uint32),
-                ("pack_ms", ctypes.c_double)]
+                ("pack_ms", ctypes.c_double),
+                ("blocks_6bit", ctypes.c_uint64), ("blocks_7bit", ctypes.c_uint64), ("blocks_raw", ctypes.c_uint64),
+                ("escaped_bytes", ctypes.c_uint64)]
 
 
 # (name, restype, argtypes) for every entry point declared in include/trivy_secret.h
@@ -160,6 +162,12 @@ SIGNATURES = [
                                            ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]),
     ("tsg_test_wire_unpack_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                                     ctypes.c_size_t, ctypes.c_void_p]),
+    ("tsg_test_wire_pack2", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p,
+                                            ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int),
+                                            ctypes.c_void_p, ctypes.c_void_p]),
+    ("tsg_test_wire_unpack2_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     ("tsg_scan_host_reference", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                                 c_char_pp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                                 ctypes.POINTER(ctypes.c_void_p)]),

@@ -486,6 +486,8 @@ int tsg_result_stats(const tsg_result* r, tsg_stats* out) {
   out->feed_ms = s.feed_ms;
   out->wire_bytes = s.wire_bytes; out->packed_strips = s.packed_strips; out->raw_strips = s.raw_strips;
   out->pack_ms = s.pack_ms;
+  out->blocks_6bit = s.blocks_6bit; out->blocks_7bit = s.blocks_7bit; out->blocks_raw = s.blocks_raw;
+  out->escaped_bytes = s.escaped_bytes;
   return TSG_OK;
   TSG_API_CATCH
 }
@@ -1082,6 +1084,42 @@ int tsg_test_wire_unpack_device(const uint8_t* packed, size_t packed_len, const 
   if (n && (!packed || !table || !out)) return fail(TSG_ERR_INVALID, "NULL argument");
   const char* msg = "";
   if (!wire_unpack_device_probe(packed, packed_len, table, n, out, &msg)) return fail(TSG_ERR_INTERNAL, msg);
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_test_wire_pack2(const uint8_t* src, size_t n, int path, uint8_t* packed, size_t packed_cap, uint32_t* table,
+                        uint8_t* alpha, size_t* packed_len, int* path_used, uint64_t* counts, uint8_t* back) {
+  TSG_API_TRY
+  if ((!src && n) || !table || !alpha || !packed_len || (!packed && packed_cap)) return fail(TSG_ERR_INVALID, "NULL argument");
+  if (path < 0 || path > 3 || n > kWireMaxStrip) return fail(TSG_ERR_INVALID, "path or length out of range");
+  std::vector<uint8_t> buf(wire2_bound(n));
+  std::vector<uint32_t> tab(wire_blocks(n) + 1);
+  std::vector<uint8_t> al(wire2_alpha_bytes(n) + 1);
+  Wire2Stats st;
+  const size_t pl = wire_pack2(src, n, buf.data(), tab.data(), al.data(), path, &st);
+  *packed_len = pl;
+  if (path_used) *path_used = wire2_path(path);
+  if (counts) { counts[0] = st.blocks6; counts[1] = st.blocks7; counts[2] = st.blocks_raw; counts[3] = st.escaped; }
+  if (pl > packed_cap) return fail(TSG_ERR_INVALID, "packed_cap is too small");
+  if (pl) memcpy(packed, buf.data(), pl);
+  memcpy(table, tab.data(), wire_blocks(n) * sizeof(uint32_t));
+  memcpy(alpha, al.data(), wire2_alpha_bytes(n));
+  if (back) {
+    // (from an exact-size copy: the reference unpack reads nothing past the packed bytes)
+    std::vector<uint8_t> exact(buf.begin(), buf.begin() + pl);
+    wire_unpack2(exact.data(), tab.data(), al.data(), n, back);
+  }
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_test_wire_unpack2_device(const uint8_t* packed, size_t packed_len, const uint32_t* table, const uint8_t* alpha,
+                                 size_t n, uint8_t* out) {
+  TSG_API_TRY
+  if (n && (!packed || !table || !alpha || !out)) return fail(TSG_ERR_INVALID, "NULL argument");
+  const char* msg = "";
+  if (!wire_unpack2_device_probe(packed, packed_len, table, alpha, n, out, &msg)) return fail(TSG_ERR_INTERNAL, msg);
   return TSG_OK;
   TSG_API_CATCH
 }

@@ -1600,7 +1600,7 @@ struct StageIn {
   const uint8_t* off_src = nullptr; uint8_t* off_dst = nullptr; uint64_t off_bytes = 0;
 };
 constexpr uint64_t kDirectStageBytes = 1u << 20;     // batches up to this size (and pinned) are staged by the prologue
-constexpr int kWirePackDefault = 1;            // TSG_WIRE_PACK unset: 1 = packers race the link (wirepack.h)
+constexpr const char* kWirePackDefault = "2";  // TSG_WIRE_PACK unset: packers race the link with the 6-bit codec (wirepack.h)
 
 // One in-flight call's resources on one device: its own streams (compute +
 // copy), timing events, the two-slot upload ring and every per-batch scratch
@@ -2025,6 +2025,8 @@ void add_stats(ScanStats* a, const ScanStats& s) {
   a->table_in_lds = s.table_in_lds;
   a->wire_bytes += s.wire_bytes; a->packed_strips += s.packed_strips; a->raw_strips += s.raw_strips;
   a->pack_ms += s.pack_ms;
+  a->blocks_6bit += s.blocks_6bit; a->blocks_7bit += s.blocks_7bit; a->blocks_raw += s.blocks_raw;
+  a->escaped_bytes += s.escaped_bytes;
   a->gather_bytes += s.gather_bytes; a->gather_runs += s.gather_runs; a->gather_ms += s.gather_ms;
   a->gather_retries += s.gather_retries;
 }
@@ -2064,8 +2066,13 @@ std::unique_ptr<Engine> Engine::create(std::shared_ptr<const Ruleset> rs, const 
   if (const char* c = std::getenv("TSG_POLL_YIELD")) e->poll_yield_ = std::atoi(c) != 0;
   if (const char* c = std::getenv("TSG_POP_SPIN_US")) e->pop_spin_us_ = std::max(0, std::min(std::atoi(c), 100000));
   if (const char* c = std::getenv("TSG_HOST_PROFILE")) e->host_profile_ = std::atoi(c) != 0;
-  e->wire_mode_ = kWirePackDefault;
-  if (const char* c = std::getenv("TSG_WIRE_PACK")) e->wire_mode_ = std::strcmp(c, "force") == 0 ? 2 : std::atoi(c) != 0 ? 1 : 0;
+  {
+    const char* c = std::getenv("TSG_WIRE_PACK");
+    if (!c) c = kWirePackDefault;
+    const bool v2 = std::strcmp(c, "force2") == 0 || std::strcmp(c, "2") == 0;
+    e->wire_codec_ = v2 ? 2 : 1;
+    e->wire_mode_ = std::strncmp(c, "force", 5) == 0 && (c[5] == 0 || v2) ? 2 : std::atoi(c) != 0 ? 1 : 0;
+  }
   if (const char* c = std::getenv("TSG_WIRE_PACK_THREADS")) e->wire_threads_n_ = std::max(0, std::min(16, std::atoi(c)));
   if (const char* c = std::getenv("TSG_WIRE_STRIP_BYTES")) {
     const long long v = std::atoll(c);
@@ -2946,8 +2953,9 @@ bool Engine::prefilter_only(const BatchInput& in, std::vector<std::vector<std::v
 // ---- wire packing of uploaded batches (wirepack.h)
 //
 // The link sets the step time of an uploaded batch, and source text is almost
-// all ASCII, so strips of a segment cross the link packed to 7 bits per byte
-// and are restored in the ring by tsg_wire_unpack before K1 reads them.  The
+// all ASCII, so strips of a segment cross the link packed (to 6-bit codes with
+// escapes or to 7 bits per byte: the engine's codec, wirepack.h) and are
+// restored in the ring by that codec's unpack kernel before K1 reads them.  The
 // engine's packer threads claim strips from the front of the feeder's segment
 // (then of the next one) and pack them into the lane's pinned staging slots; the scan's feeder thread
 // owns the copy stream, keeps kWireCopiesAhead strip copies queued and, when
@@ -2959,6 +2967,8 @@ bool Engine::prefilter_only(const BatchInput& in, std::vector<std::vector<std::v
 constexpr size_t kWireCopiesAhead = 3;
 
 void wire_unpack_launch(const uint8_t* land, uint32_t tab_bytes, uint8_t* dst, uint32_t n, hipStream_t stream);
+void wire_unpack2_launch(const uint8_t* land, uint32_t tab_bytes, uint32_t alpha_bytes, uint8_t* dst, uint32_t n,
+                         hipStream_t stream);
 
 struct WireFeed {
   Engine* eng = nullptr;
@@ -2968,6 +2978,7 @@ struct WireFeed {
   int device = 0;
   uint64_t strip = 0;
   bool force = false;                  // the feeder waits for the packers instead of sending raw strips
+  bool v2 = false;                     // the 6-bit codec (wirepack.h); else the 7-bit one
   int npackers = 0;
   bool timeline = false;
   std::mutex mu;                       // guards everything below
@@ -2981,7 +2992,7 @@ struct WireFeed {
   std::vector<Span> span;
   size_t feed_seg = 0;
   enum { kFree, kPacking, kReady, kFlying };
-  struct Slot { int state = kFree; size_t seg = 0; uint32_t strip = 0; uint64_t wire_len = 0; };
+  struct Slot { int state = kFree; size_t seg = 0; uint32_t strip = 0; uint64_t wire_len = 0; Wire2Stats modes; };
   std::vector<Slot> slots;
   std::deque<int> ready;
   int nfree = 0;
@@ -2991,6 +3002,7 @@ struct WireFeed {
   size_t segs_recorded = 0;            // feeder: segments whose up_done is recorded
   uint64_t wire_bytes = 0;
   uint32_t packed = 0, raw = 0;
+  Wire2Stats modes;                    // of the strips sent packed
   double pack_ms = 0;
   std::thread feeder;
   // feeder only: copies in flight (slot -1: a raw strip), unpacks in flight
@@ -3053,13 +3065,23 @@ void WireFeed::pack_loop() {
     auto t0 = std::chrono::steady_clock::now();
     Lane::WireSlot& w = ln->wire[id];
     const size_t tab = wire_table_bytes(n);
-    const size_t pl = wire_pack(p, n, w.h + tab, reinterpret_cast<uint32_t*>(w.h), kWireAuto);
+    uint32_t* table = reinterpret_cast<uint32_t*>(w.h);
+    size_t head = tab, pl;
+    Wire2Stats modes;
+    if (v2) {
+      head += wire2_alpha_bytes(n);
+      pl = wire_pack2(p, n, w.h + head, table, w.h + tab, kWireAuto, &modes);
+    } else {
+      pl = wire_pack(p, n, w.h + tab, table, kWireAuto);
+      for (size_t b = 0; b < wire_blocks(n); ++b) ++(table[b] & kWireRawBit ? modes.blocks_raw : modes.blocks7);
+    }
     const double ms = ms_since(t0);
     lk.lock();
     pack_ms += ms;
     slots[id].seg = sgi;
     slots[id].strip = s;
-    slots[id].wire_len = tab + pl;
+    slots[id].wire_len = head + pl;
+    slots[id].modes = modes;
     slots[id].state = kReady;
     ready.push_back(id);
     cv.notify_all();
@@ -3108,6 +3130,7 @@ bool WireFeed::feed_segment(size_t si, std::string* err) {
   cv.notify_all();
   uint64_t sent = 0;
   uint32_t npacked = 0, nraw = 0;
+  Wire2Stats modes;
   for (uint32_t issued = 0; issued < ns;) {
     if (!reap(err)) return false;
     int id = -1;
@@ -3160,14 +3183,25 @@ bool WireFeed::feed_segment(size_t si, std::string* err) {
       HIP_OK(hipMemcpyAsync(w.d, w.h, wire_len, hipMemcpyHostToDevice, ln->copy));
       HIP_OK(hipEventRecord(w.copied, ln->copy));
       HIP_OK(hipStreamWaitEvent(ln->unpack, w.copied, 0));
-      wire_unpack_launch(w.d, static_cast<uint32_t>(wire_table_bytes(n)), ln->ring[slot].p + o, static_cast<uint32_t>(n),
-                         ln->unpack);
+      if (v2) {
+        wire_unpack2_launch(w.d, static_cast<uint32_t>(wire_table_bytes(n)), static_cast<uint32_t>(wire2_alpha_bytes(n)),
+                            ln->ring[slot].p + o, static_cast<uint32_t>(n), ln->unpack);
+      } else {
+        wire_unpack_launch(w.d, static_cast<uint32_t>(wire_table_bytes(n)), ln->ring[slot].p + o, static_cast<uint32_t>(n),
+                           ln->unpack);
+      }
       HIP_OK(hipGetLastError());
       HIP_OK(hipEventRecord(w.unpacked, ln->unpack));
       copies.push_back({w.copied, id});
       unpacks.push_back({w.unpacked, id});
       sent += wire_len;
       ++npacked;
+      {
+        // (the slot is this thread's until its unpack is reaped)
+        const Wire2Stats& m = slots[id].modes;
+        modes.blocks6 += m.blocks6; modes.blocks7 += m.blocks7; modes.blocks_raw += m.blocks_raw;
+        modes.escaped += m.escaped;
+      }
     }
     ++issued;
   }
@@ -3181,10 +3215,16 @@ bool WireFeed::feed_segment(size_t si, std::string* err) {
     wire_bytes += sent;
     packed += npacked;
     raw += nraw;
+    this->modes.blocks6 += modes.blocks6; this->modes.blocks7 += modes.blocks7;
+    this->modes.blocks_raw += modes.blocks_raw; this->modes.escaped += modes.escaped;
   }
   cv.notify_all();
-  if (timeline) std::fprintf(stderr, "[tsg tl] seg %zu wire: %u strips packed, %u raw, %llu bytes sent\n", si, npacked,
-                             nraw, static_cast<unsigned long long>(sent));
+  if (timeline) std::fprintf(stderr, "[tsg tl] seg %zu wire: %u strips packed, %u raw, %llu bytes sent; blocks 6-bit %llu, "
+                             "7-bit %llu, raw %llu, %llu bytes escaped\n", si, npacked, nraw,
+                             static_cast<unsigned long long>(sent), static_cast<unsigned long long>(modes.blocks6),
+                             static_cast<unsigned long long>(modes.blocks7),
+                             static_cast<unsigned long long>(modes.blocks_raw),
+                             static_cast<unsigned long long>(modes.escaped));
   return true;
 }
 
@@ -3235,6 +3275,7 @@ bool WireFeed::start(Engine& eng, Lane* ln, int device, const std::vector<Segmen
   f->device = device;
   f->strip = eng.wire_strip_;
   f->force = eng.wire_mode_ == 2;
+  f->v2 = eng.wire_codec_ == 2;
   f->npackers = np;
   f->timeline = eng.host_profile_;
   f->slots.resize(nslots);
@@ -3250,7 +3291,10 @@ bool WireFeed::start(Engine& eng, Lane* ln, int device, const std::vector<Segmen
   }
   *out = std::move(f);
   WireFeed* w = out->get();
-  if (!ln->ensure_wire(nslots, wire_table_bytes(w->strip) + wire_bound(w->strip), err)) return false;
+  // (slots fit either codec's head and bound, so a lane serves engines of both)
+  if (!ln->ensure_wire(nslots, wire_table_bytes(w->strip) + wire2_alpha_bytes(w->strip) +
+                                   std::max(wire_bound(w->strip), wire2_bound(w->strip)), err))
+    return false;
   {
     std::lock_guard<std::mutex> lk(eng.wire_mu_);
     while (static_cast<int>(eng.wire_threads_.size()) < np) eng.wire_threads_.emplace_back([e = &eng] { e->wire_packer_main(); });
@@ -3272,11 +3316,16 @@ void WireFeed::wind_down(ScanStats* st) {
     eng->wire_cv_.wait(lk, [&] { return eng->wire_active_ == 0; });
     eng->wire_busy_ = false;
   }
-  if (timeline) std::fprintf(stderr, "[tsg tl] wire: %d packers busy %.3f ms in all\n", npackers, pack_ms);
+  if (timeline) std::fprintf(stderr, "[tsg tl] wire: %d packers busy %.3f ms in all (%s codec, path %d)\n", npackers,
+                             pack_ms, v2 ? "6-bit" : "7-bit", v2 ? wire2_path(kWireAuto) : wire_have_avx2() ? 2 : 1);
   st->wire_bytes += wire_bytes;
   st->packed_strips += packed;
   st->raw_strips += raw;
   st->pack_ms += pack_ms;
+  st->blocks_6bit += modes.blocks6;
+  st->blocks_7bit += modes.blocks7;
+  st->blocks_raw += modes.blocks_raw;
+  st->escaped_bytes += modes.escaped;
 }
 
 void Engine::wire_packer_main() {

@@ -1,7 +1,9 @@
-// Host side of the wire packing (wirepack.h): a scalar 64-bit SWAR path and an
-// AVX2 path, chosen at run time, and the reference unpack.
+// Host side of the wire packing (wirepack.h).  The 7-bit codec: a scalar 64-bit
+// SWAR path and an AVX2 path, chosen at run time, and the reference unpack.  The
+// 6-bit codec with escapes: scalar, AVX2 and AVX-512 VBMI paths and its unpack.
 #include "wirepack.h"
 
+#include <algorithm>
 #include <cstring>
 
 #if defined(__x86_64__)
@@ -114,6 +116,19 @@ size_t wire_pack(const uint8_t* src, size_t n, uint8_t* dst, uint32_t* table, in
   return o;
 }
 
+namespace {
+
+void unpack7_block(const uint8_t* s, size_t len, uint8_t* d) {
+  for (size_t g = 0; 8 * g < len; ++g) {
+    uint64_t v = 0;
+    std::memcpy(&v, s + 7 * g, 7);
+    const uint64_t x = spread(v);
+    std::memcpy(d + 8 * g, &x, len - 8 * g < 8 ? len - 8 * g : 8);
+  }
+}
+
+}  // namespace
+
 void wire_unpack(const uint8_t* packed, const uint32_t* table, size_t n, uint8_t* dst) {
   const size_t nb = wire_blocks(n);
   for (size_t b = 0; b < nb; ++b) {
@@ -124,11 +139,244 @@ void wire_unpack(const uint8_t* packed, const uint32_t* table, size_t n, uint8_t
       std::memcpy(d, s, len);
       continue;
     }
-    for (size_t g = 0; 8 * g < len; ++g) {
-      uint64_t v = 0;
-      std::memcpy(&v, s + 7 * g, 7);
-      const uint64_t x = spread(v);
-      std::memcpy(d + 8 * g, &x, len - 8 * g < 8 ? len - 8 * g : 8);
+    unpack7_block(s, len, d);
+  }
+}
+
+// ---- v2: 6-bit codes with escapes (wirepack.h)
+
+namespace {
+
+constexpr uint32_t kAbort = ~0u;
+
+// What the packers look bytes up in, per region: code[v] for the scalar path,
+// and inv[v] = 63 - code[v] for v < 0x80 (zero for a byte that escapes), which
+// the AVX2 path reads as eight 16-entry tables and the VBMI path as two
+// 64-entry ones.
+struct Alphabet {
+  uint8_t code[256];
+  alignas(64) uint8_t inv[128];
+};
+
+void choose_alphabet(const uint8_t* p, size_t len, uint8_t* vals, Alphabet* a) {
+  uint32_t key[128];
+  for (uint32_t v = 0; v < 128; ++v) key[v] = 127 - v;
+  for (size_t i = 0; i < len; i += kWire2Sample)
+    if (p[i] < 0x80) key[p[i]] += 256;             // (at most 1024 samples: the count stays above the value)
+  // larger count first, then lower value
+  std::partial_sort(key, key + kWire2Escape, key + 128, [](uint32_t x, uint32_t y) { return x > y; });
+  std::memset(a->code, kWire2Escape, sizeof a->code);
+  std::memset(a->inv, 0, sizeof a->inv);
+  for (uint32_t c = 0; c < kWire2Escape; ++c) {
+    const uint8_t v = static_cast<uint8_t>(127 - (key[c] & 0xFF));
+    vals[c] = v;
+    a->code[v] = static_cast<uint8_t>(c);
+    a->inv[v] = static_cast<uint8_t>(kWire2Escape - c);
+  }
+  vals[kWire2Escape] = 0;
+}
+
+// The 6-bit codes of groups [g0, ...) of a block of len bytes (4 bytes -> 3),
+// escaped bytes appended to esc; returns the new escape count, or kAbort once
+// it reaches `limit`.  *acc gathers the OR of the bytes.
+inline uint32_t pack6_groups_scalar(const uint8_t* src, size_t len, size_t g0, const Alphabet& a, uint8_t* dst,
+                                    uint8_t* esc, uint32_t nesc, uint32_t limit, uint32_t* acc) {
+  const size_t ng = (len + 3) / 4;
+  for (size_t g = g0; g < ng; ++g) {
+    uint32_t v = 0;
+    const size_t k = len - 4 * g < 4 ? len - 4 * g : 4;
+    for (size_t j = 0; j < k; ++j) {
+      const uint8_t x = src[4 * g + j];
+      const uint32_t c = a.code[x];
+      *acc |= x;
+      v |= c << (6 * j);
+      if (c == kWire2Escape) esc[nesc++] = x;
+    }
+    dst[3 * g] = static_cast<uint8_t>(v);
+    dst[3 * g + 1] = static_cast<uint8_t>(v >> 8);
+    dst[3 * g + 2] = static_cast<uint8_t>(v >> 16);
+    if (nesc >= limit) return kAbort;
+  }
+  return nesc;
+}
+
+uint32_t pack6_scalar(const uint8_t* src, size_t len, const Alphabet& a, uint8_t* dst, uint8_t* esc, uint32_t limit,
+                      uint32_t* acc) {
+  return pack6_groups_scalar(src, len, 0, a, dst, esc, 0, limit, acc);
+}
+
+#if defined(__x86_64__)
+// (the stores of both vector paths run up to 16 bytes past the codes they
+// hold: over the codes that follow, or into what is written after them)
+__attribute__((target("avx2"))) uint32_t pack6_avx2(const uint8_t* src, size_t len, const Alphabet& a, uint8_t* dst,
+                                                     uint8_t* esc, uint32_t limit, uint32_t* acc) {
+  __m256i T[8], X[8];
+  for (int k = 0; k < 8; ++k) {
+    T[k] = _mm256_broadcastsi128_si256(_mm_load_si128(reinterpret_cast<const __m128i*>(a.inv + 16 * k)));
+    X[k] = _mm256_set1_epi8(static_cast<char>(16 * k));
+  }
+  const __m256i k70 = _mm256_set1_epi8(0x70), k63 = _mm256_set1_epi8(63);
+  const __m256i mul1 = _mm256_set1_epi16(0x4001), mul2 = _mm256_set1_epi32(0x10000001);
+  const __m256i shuf = _mm256_setr_epi8(0, 1, 2, 4, 5, 6, 8, 9, 10, 12, 13, 14, -1, -1, -1, -1,
+                                        0, 1, 2, 4, 5, 6, 8, 9, 10, 12, 13, 14, -1, -1, -1, -1);
+  __m256i vacc = _mm256_setzero_si256();
+  uint32_t nesc = 0;
+  const size_t nv = len / 32;
+  for (size_t i = 0; i < nv; ++i) {
+    const __m256i x = _mm256_loadu_si256(reinterpret_cast<const __m256i*>(src + 32 * i));
+    vacc = _mm256_or_si256(vacc, x);
+    // table k answers for the bytes whose high nibble is k: the saturating
+    // add leaves their low nibble and sets bit 7 of every other byte
+    __m256i r = _mm256_shuffle_epi8(T[0], _mm256_adds_epu8(x, k70));
+    for (int k = 1; k < 8; ++k)
+      r = _mm256_or_si256(r, _mm256_shuffle_epi8(T[k], _mm256_adds_epu8(_mm256_xor_si256(x, X[k]), k70)));
+    const __m256i c = _mm256_sub_epi8(k63, r);
+    uint32_t m = static_cast<uint32_t>(_mm256_movemask_epi8(_mm256_cmpeq_epi8(c, k63)));
+    __m256i p = _mm256_madd_epi16(_mm256_maddubs_epi16(c, mul1), mul2);
+    p = _mm256_shuffle_epi8(p, shuf);
+    _mm_storeu_si128(reinterpret_cast<__m128i*>(dst + 24 * i), _mm256_castsi256_si128(p));
+    _mm_storeu_si128(reinterpret_cast<__m128i*>(dst + 24 * i + 12), _mm256_extracti128_si256(p, 1));
+    if (m) {
+      for (; m; m &= m - 1) esc[nesc++] = src[32 * i + static_cast<unsigned>(__builtin_ctz(m))];
+      if (nesc >= limit) return kAbort;
+    }
+  }
+  const __m128i v = _mm_or_si128(_mm256_castsi256_si128(vacc), _mm256_extracti128_si256(vacc, 1));
+  const uint64_t r = static_cast<uint64_t>(_mm_cvtsi128_si64(v)) | static_cast<uint64_t>(_mm_extract_epi64(v, 1));
+  *acc |= (r & kHigh) ? 0x80u : 0u;
+  return pack6_groups_scalar(src, len, nv * 8, a, dst, esc, nesc, limit, acc);
+}
+
+__attribute__((target("avx512f,avx512bw,avx512vl,avx512vbmi"))) uint32_t pack6_vbmi(const uint8_t* src, size_t len,
+                                                                                     const Alphabet& a, uint8_t* dst,
+                                                                                     uint8_t* esc, uint32_t limit,
+                                                                                     uint32_t* acc) {
+  const __m512i t0 = _mm512_load_si512(a.inv), t1 = _mm512_load_si512(a.inv + 64);
+  const __m512i k63 = _mm512_set1_epi8(63);
+  const __m512i mul1 = _mm512_set1_epi16(0x4001), mul2 = _mm512_set1_epi32(0x10000001);
+  alignas(64) uint8_t idx[64];
+  for (int j = 0; j < 64; ++j) idx[j] = static_cast<uint8_t>(j < 48 ? j / 3 * 4 + j % 3 : 0);
+  const __m512i gather = _mm512_load_si512(idx);
+  __mmask64 high = 0;
+  uint32_t nesc = 0;
+  const size_t nv = len / 64;
+  for (size_t i = 0; i < nv; ++i) {
+    const __m512i x = _mm512_loadu_si512(src + 64 * i);
+    const __mmask64 hi = _mm512_movepi8_mask(x);
+    high |= hi;
+    // (the permute reads index bits 0..6: bytes >= 0x80 are set to the escape code after it)
+    const __m512i r = _mm512_permutex2var_epi8(t0, x, t1);
+    const __m512i c = _mm512_mask_mov_epi8(_mm512_sub_epi8(k63, r), hi, k63);
+    uint64_t m = _mm512_cmpeq_epi8_mask(c, k63);
+    __m512i p = _mm512_madd_epi16(_mm512_maddubs_epi16(c, mul1), mul2);
+    p = _mm512_permutexvar_epi8(gather, p);
+    _mm512_storeu_si512(dst + 48 * i, p);
+    if (m) {
+      for (; m; m &= m - 1) esc[nesc++] = src[64 * i + static_cast<unsigned>(__builtin_ctzll(m))];
+      if (nesc >= limit) return kAbort;
+    }
+  }
+  *acc |= high ? 0x80u : 0u;
+  return pack6_groups_scalar(src, len, nv * 16, a, dst, esc, nesc, limit, acc);
+}
+#endif
+
+}  // namespace
+
+bool wire_have_vbmi() {
+#if defined(__x86_64__)
+  static const bool have = __builtin_cpu_supports("avx512f") && __builtin_cpu_supports("avx512bw") &&
+                           __builtin_cpu_supports("avx512vl") && __builtin_cpu_supports("avx512vbmi");
+  return have;
+#else
+  return false;
+#endif
+}
+
+int wire2_path(int path) {
+  if (path == kWireScalar) return kWireScalar;
+  if (path != kWireAvx2 && wire_have_vbmi()) return kWireVbmi;
+  return wire_have_avx2() ? kWireAvx2 : kWireScalar;
+}
+
+size_t wire_pack2(const uint8_t* src, size_t n, uint8_t* dst, uint32_t* table, uint8_t* alpha, int path,
+                  Wire2Stats* stats) {
+  uint32_t (*pack6)(const uint8_t*, size_t, const Alphabet&, uint8_t*, uint8_t*, uint32_t, uint32_t*) = pack6_scalar;
+  uint64_t (*pack7)(const uint8_t*, size_t, uint8_t*) = pack_block_scalar;
+#if defined(__x86_64__)
+  const int used = wire2_path(path);
+  if (used != kWireScalar) pack7 = pack_block_avx2;
+  if (used == kWireAvx2) pack6 = pack6_avx2;
+  if (used == kWireVbmi) pack6 = pack6_vbmi;
+#endif
+  if (n) std::memset(alpha, 0, wire2_alpha_bytes(n));
+  Wire2Stats st;
+  Alphabet a;
+  uint8_t esc[kWireBlock + 64];
+  size_t o = 0;
+  const size_t nb = wire_blocks(n);
+  for (size_t b = 0; b < nb; ++b) {
+    const size_t at = b * kWireBlock;
+    if (at % kWire2Region == 0)
+      choose_alphabet(src + at, n - at < kWire2Region ? n - at : kWire2Region, alpha + at / kWire2Region * kWire2Alpha, &a);
+    const uint8_t* s = src + at;
+    const size_t len = n - at < kWireBlock ? n - at : kWireBlock;
+    const size_t cb = wire2_code_bytes(len);
+    // 6-bit is chosen only below the raw size: once cb + escapes reach len it is out
+    const uint32_t limit = len > cb ? static_cast<uint32_t>(len - cb) : 0;
+    uint32_t acc = 0;
+    const uint32_t nesc = limit ? pack6(s, len, a, dst + o, esc, limit, &acc) : kAbort;
+    if (nesc != kAbort) {
+      const size_t size6 = cb + ((nesc + 15) & ~size_t(15));
+      const bool ascii = !(acc & 0x80);
+      if (size6 < len && !(ascii && wire_packed_len(len) <= size6)) {
+        const size_t codes = (len + 3) / 4 * 3;
+        std::memset(dst + o + codes, 0, cb - codes);
+        std::memcpy(dst + o + cb, esc, nesc);
+        std::memset(dst + o + cb + nesc, 0, size6 - cb - nesc);
+        table[b] = static_cast<uint32_t>(o) | kWire6Bit;
+        o += size6;
+        ++st.blocks6;
+        st.escaped += nesc;
+        continue;
+      }
+    }
+    // 7-bit if the block is ASCII and that is below the raw size, else raw
+    if (wire_packed_len(len) < len && !(pack7(s, len, dst + o) & kHigh)) {
+      table[b] = static_cast<uint32_t>(o);
+      o += wire_packed_len(len);
+      ++st.blocks7;
+    } else {
+      std::memcpy(dst + o, s, len);
+      table[b] = static_cast<uint32_t>(o) | kWireRawBit;
+      o += len;
+      ++st.blocks_raw;
+    }
+  }
+  if (stats) *stats = st;
+  return o;
+}
+
+void wire_unpack2(const uint8_t* packed, const uint32_t* table, const uint8_t* alpha, size_t n, uint8_t* dst) {
+  const size_t nb = wire_blocks(n);
+  for (size_t b = 0; b < nb; ++b) {
+    const size_t at = b * kWireBlock;
+    const size_t len = n - at < kWireBlock ? n - at : kWireBlock;
+    const uint8_t* s = packed + (table[b] & ~(kWireRawBit | kWire6Bit));
+    uint8_t* d = dst + at;
+    if (table[b] & kWireRawBit) {
+      std::memcpy(d, s, len);
+    } else if (table[b] & kWire6Bit) {
+      const uint8_t* al = alpha + at / kWire2Region * kWire2Alpha;
+      const uint8_t* e = s + wire2_code_bytes(len);
+      for (size_t i = 0; i < len; ++i) {
+        const size_t bit = 6 * i;
+        const uint32_t lo = s[bit >> 3], hi = (bit & 7) > 2 ? s[(bit >> 3) + 1] : 0;
+        const uint32_t c = ((lo | hi << 8) >> (bit & 7)) & 63;
+        d[i] = c == kWire2Escape ? *e++ : al[c];
+      }
+    } else {
+      unpack7_block(s, len, d);
     }
   }
 }

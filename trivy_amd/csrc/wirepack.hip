@@ -1,6 +1,6 @@
 // Device side of the wire packing (wirepack.h): restores a packed strip that
 // the copy engine landed in a device buffer to its original bytes in the
-// upload ring, before K1 reads them.
+// upload ring, before K1 reads them; one kernel per codec.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -16,6 +16,51 @@ __device__ __forceinline__ unsigned long long wire_spread(unsigned long long v) 
   unsigned long long x = (v & 0x000000000FFFFFFFull) | ((v << 4) & 0x0FFFFFFF00000000ull);
   x = (x & 0x00003FFF00003FFFull) | ((x << 2) & 0x3FFF00003FFF0000ull);
   return (x & 0x007F007F007F007Full) | ((x << 1) & 0x7F007F007F007F00ull);
+}
+
+// Lane t's 16 bytes of a 7-bit block of len bytes whose packed form is in sh:
+// its 14 bytes (two groups) from the four dwords that hold them, stored as one
+// 16-byte word (single bytes where the block ends inside them).
+__device__ __forceinline__ void unpack7_lane(const uint4* sh, uint32_t t, uint32_t len, uint8_t* __restrict__ out) {
+  if (16 * t >= len) return;
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(sh) + ((14 * t) >> 2);
+  const unsigned long long lo = w[0] | (static_cast<unsigned long long>(w[1]) << 32);
+  const unsigned long long hi = w[2] | (static_cast<unsigned long long>(w[3]) << 32);
+  const unsigned long long m56 = (1ull << 56) - 1;
+  // the lane's 112 bits start at bit 0 or bit 16 of lo:hi
+  const bool odd = (14 * t) & 2;
+  const unsigned long long g0 = (odd ? (lo >> 16) | (hi << 48) : lo) & m56;
+  const unsigned long long g1 = (odd ? hi >> 8 : (lo >> 56) | (hi << 8)) & m56;
+  const unsigned long long x0 = wire_spread(g0), x1 = wire_spread(g1);
+  if (16 * t + 16 <= len) {
+    uint4 v;
+    v.x = static_cast<uint32_t>(x0); v.y = static_cast<uint32_t>(x0 >> 32);
+    v.z = static_cast<uint32_t>(x1); v.w = static_cast<uint32_t>(x1 >> 32);
+    reinterpret_cast<uint4*>(out)[t] = v;
+  } else {
+    for (uint32_t i = 16 * t; i < len; ++i) {
+      const uint32_t k = i - 16 * t;
+      out[i] = static_cast<uint8_t>((k < 8 ? x0 : x1) >> (8 * (k & 7)));
+    }
+  }
+}
+
+__device__ __forceinline__ void copy_raw_lane(const uint8_t* __restrict__ src, uint32_t t, uint32_t len,
+                                              uint8_t* __restrict__ out) {
+  if (16 * t + 16 <= len) {
+    reinterpret_cast<uint4*>(out)[t] = reinterpret_cast<const uint4*>(src)[t];
+  } else {
+    for (uint32_t i = 16 * t; i < len; ++i) out[i] = src[i];
+  }
+}
+
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t lane) {
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const uint32_t u = __shfl_up(v, d);
+    if (lane >= d) v += u;
+  }
+  return v;
 }
 
 }  // namespace
@@ -42,39 +87,97 @@ __global__ __launch_bounds__(256) void tsg_wire_unpack(const uint8_t* __restrict
     const uint8_t* __restrict__ src = data + (ent & ~kWireRawBit);
     uint8_t* __restrict__ out = dst + static_cast<size_t>(b) * kWireBlock;
     if (ent & kWireRawBit) {             // (uniform over the workgroup)
-      if (16 * t + 16 <= len) {
-        reinterpret_cast<uint4*>(out)[t] = reinterpret_cast<const uint4*>(src)[t];
-      } else {
-        for (uint32_t i = 16 * t; i < len; ++i) out[i] = src[i];
-      }
+      copy_raw_lane(src, t, len, out);
       continue;
     }
     const uint32_t pl = (len + 7) / 8 * 7;
     if (16 * t < pl) sh[t] = reinterpret_cast<const uint4*>(src)[t];
     __syncthreads();
-    if (16 * t < len) {
-      const uint32_t* w = reinterpret_cast<const uint32_t*>(sh) + ((14 * t) >> 2);
-      const unsigned long long lo = w[0] | (static_cast<unsigned long long>(w[1]) << 32);
-      const unsigned long long hi = w[2] | (static_cast<unsigned long long>(w[3]) << 32);
-      const unsigned long long m56 = (1ull << 56) - 1;
-      // the lane's 112 bits start at bit 0 or bit 16 of lo:hi
-      const bool odd = (14 * t) & 2;
-      const unsigned long long g0 = (odd ? (lo >> 16) | (hi << 48) : lo) & m56;
-      const unsigned long long g1 = (odd ? hi >> 8 : (lo >> 56) | (hi << 8)) & m56;
-      const unsigned long long x0 = wire_spread(g0), x1 = wire_spread(g1);
-      if (16 * t + 16 <= len) {
-        uint4 v;
-        v.x = static_cast<uint32_t>(x0); v.y = static_cast<uint32_t>(x0 >> 32);
-        v.z = static_cast<uint32_t>(x1); v.w = static_cast<uint32_t>(x1 >> 32);
-        reinterpret_cast<uint4*>(out)[t] = v;
+    unpack7_lane(sh, t, len, out);
+    __syncthreads();                     // sh is reloaded by the next block
+  }
+}
+
+// The v2 unpack (wirepack.h): the same grid and blocks, three modes.  land =
+// the block table (tab_bytes), the alphabets (alpha_bytes, 64 bytes per region
+// of 16 blocks) and the packed bytes.  Raw and 7-bit blocks go as in
+// tsg_wire_unpack.  A 6-bit block's codes (at most 3072 bytes, a multiple of
+// 16) and its region's alphabet go to LDS; lane t owns code bytes 12t..12t+11
+// (three dwords), that is 16 codes and 16 output bytes.  Each lane counts the
+// escape codes among its codes below len, an exclusive scan over the workgroup
+// (a wave scan and the four wave totals in LDS) gives its first escaped byte,
+// and it reads those from the block's tail in global memory.  Loads of a 6-bit
+// block stay inside its payload; a short 7-bit block's may run up to 15 bytes
+// past it (kWireSlack).  Nothing is stored at or past dst + n.
+__global__ __launch_bounds__(256) void tsg_wire_unpack2(const uint8_t* __restrict__ land, uint32_t tab_bytes,
+                                                         uint32_t alpha_bytes, uint8_t* __restrict__ dst, uint32_t n) {
+  __shared__ uint4 sh[kWireBlockPacked / 16];
+  __shared__ uint4 sh_alpha[kWire2Alpha / 16];
+  __shared__ uint32_t sh_wave[4];
+  const uint32_t* __restrict__ tab = reinterpret_cast<const uint32_t*>(land);
+  const uint8_t* __restrict__ alphas = land + tab_bytes;
+  const uint8_t* __restrict__ data = alphas + alpha_bytes;
+  const uint32_t nb = (n + kWireBlock - 1) / kWireBlock;
+  const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+  for (uint32_t b = blockIdx.x; b < nb; b += gridDim.x) {
+    const uint32_t ent = tab[b];
+    const uint32_t len = min(kWireBlock, n - b * kWireBlock);
+    const uint8_t* __restrict__ src = data + (ent & ~(kWireRawBit | kWire6Bit));
+    uint8_t* __restrict__ out = dst + static_cast<size_t>(b) * kWireBlock;
+    if (ent & kWireRawBit) {             // (the mode is uniform over the workgroup)
+      copy_raw_lane(src, t, len, out);
+      continue;
+    }
+    if (!(ent & kWire6Bit)) {
+      const uint32_t pl = (len + 7) / 8 * 7;
+      if (16 * t < pl) sh[t] = reinterpret_cast<const uint4*>(src)[t];
+      __syncthreads();
+      unpack7_lane(sh, t, len, out);
+      __syncthreads();
+      continue;
+    }
+    const uint32_t cb = ((len + 3) / 4 * 3 + 15u) & ~15u;
+    if (16 * t < cb) sh[t] = reinterpret_cast<const uint4*>(src)[t];
+    if (t < kWire2Alpha / 16)
+      sh_alpha[t] = reinterpret_cast<const uint4*>(alphas + static_cast<size_t>(b / (kWire2Region / kWireBlock)) * kWire2Alpha)[t];
+    __syncthreads();
+    const uint32_t mine = 16 * t < len ? min(16u, len - 16 * t) : 0u;   // output bytes of this lane
+    uint32_t g[4] = {0, 0, 0, 0};        // four codes (24 bits) each
+    uint32_t nesc = 0;
+    if (mine) {
+      const uint32_t* w = reinterpret_cast<const uint32_t*>(sh) + 3 * t;
+      const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
+      g[0] = w0 & 0xFFFFFFu;
+      g[1] = ((w0 >> 24) | (w1 << 8)) & 0xFFFFFFu;
+      g[2] = ((w1 >> 16) | (w2 << 16)) & 0xFFFFFFu;
+      g[3] = w2 >> 8;
+#pragma unroll
+      for (uint32_t k = 0; k < 16; ++k)
+        nesc += (k < mine && ((g[k >> 2] >> (6 * (k & 3))) & 63u) == kWire2Escape) ? 1u : 0u;
+    }
+    const uint32_t incl = wave_incl_scan(nesc, lane);
+    if (lane == 63) sh_wave[wave] = incl;
+    __syncthreads();
+    uint32_t e = incl - nesc;            // index of the lane's first escaped byte
+    for (uint32_t v = 0; v < wave; ++v) e += sh_wave[v];
+    if (mine) {
+      const uint8_t* __restrict__ esc = src + cb;
+      const uint8_t* al = reinterpret_cast<const uint8_t*>(sh_alpha);
+      uint32_t o[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (uint32_t k = 0; k < 16; ++k) {
+        const uint32_t c = (g[k >> 2] >> (6 * (k & 3))) & 63u;
+        uint32_t v = al[c];
+        if (c == kWire2Escape && k < mine) v = esc[e++];
+        o[k >> 2] |= v << (8 * (k & 3));
+      }
+      if (mine == 16) {
+        reinterpret_cast<uint4*>(out)[t] = make_uint4(o[0], o[1], o[2], o[3]);
       } else {
-        for (uint32_t i = 16 * t; i < len; ++i) {
-          const uint32_t k = i - 16 * t;
-          out[i] = static_cast<uint8_t>((k < 8 ? x0 : x1) >> (8 * (k & 7)));
-        }
+        for (uint32_t k = 0; k < mine; ++k) out[16 * t + k] = static_cast<uint8_t>(o[k >> 2] >> (8 * (k & 3)));
       }
     }
-    __syncthreads();                     // sh is reloaded by the next block
+    __syncthreads();                     // sh, sh_alpha and sh_wave are rewritten by the next block
   }
 }
 
@@ -84,15 +187,28 @@ void wire_unpack_launch(const uint8_t* land, uint32_t tab_bytes, uint8_t* dst, u
   hipLaunchKernelGGL(tsg_wire_unpack, dim3(nb < 4096u ? nb : 4096u), dim3(256), 0, stream, land, tab_bytes, dst, n);
 }
 
-bool wire_unpack_device_probe(const uint8_t* packed, size_t packed_len, const uint32_t* table, size_t n, uint8_t* out,
-                              const char** err) {
+void wire_unpack2_launch(const uint8_t* land, uint32_t tab_bytes, uint32_t alpha_bytes, uint8_t* dst, uint32_t n,
+                         hipStream_t stream) {
+  const uint32_t nb = static_cast<uint32_t>(wire_blocks(n));
+  if (nb == 0) return;
+  hipLaunchKernelGGL(tsg_wire_unpack2, dim3(nb < 4096u ? nb : 4096u), dim3(256), 0, stream, land, tab_bytes, alpha_bytes,
+                     dst, n);
+}
+
+namespace {
+
+// Lands a packed strip (the table, for v2 the alphabets, the packed bytes) on
+// device 0, runs the codec's unpack kernel and reads the n bytes back.
+bool unpack_probe(const uint8_t* packed, size_t packed_len, const uint32_t* table, const uint8_t* alpha, size_t n,
+                  uint8_t* out, const char** err) {
   *err = "";
   if (n == 0) return true;
   if (n > kWireMaxStrip) { *err = "strip too large"; return false; }
-  const size_t tab = wire_table_bytes(n), guard = 64;
-  std::vector<uint8_t> h(tab + packed_len + kWireSlack, 0);
+  const size_t tab = wire_table_bytes(n), al = alpha ? wire2_alpha_bytes(n) : 0, guard = 64;
+  std::vector<uint8_t> h(tab + al + packed_len + kWireSlack, 0);
   std::memcpy(h.data(), table, wire_blocks(n) * sizeof(uint32_t));
-  std::memcpy(h.data() + tab, packed, packed_len);
+  if (alpha) std::memcpy(h.data() + tab, alpha, al);
+  std::memcpy(h.data() + tab + al, packed, packed_len);
   std::vector<uint8_t> back(n + guard);
   uint8_t *d_land = nullptr, *d_out = nullptr;
   bool ok = hipSetDevice(0) == hipSuccess && hipMalloc(&d_land, h.size()) == hipSuccess &&
@@ -100,7 +216,12 @@ bool wire_unpack_device_probe(const uint8_t* packed, size_t packed_len, const ui
             hipMemcpy(d_land, h.data(), h.size(), hipMemcpyHostToDevice) == hipSuccess &&
             hipMemset(d_out, 0xA5, n + guard) == hipSuccess;
   if (ok) {
-    wire_unpack_launch(d_land, static_cast<uint32_t>(tab), d_out, static_cast<uint32_t>(n), nullptr);
+    if (alpha) {
+      wire_unpack2_launch(d_land, static_cast<uint32_t>(tab), static_cast<uint32_t>(al), d_out, static_cast<uint32_t>(n),
+                          nullptr);
+    } else {
+      wire_unpack_launch(d_land, static_cast<uint32_t>(tab), d_out, static_cast<uint32_t>(n), nullptr);
+    }
     ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
          hipMemcpy(back.data(), d_out, n + guard, hipMemcpyDeviceToHost) == hipSuccess;
   }
@@ -112,6 +233,18 @@ bool wire_unpack_device_probe(const uint8_t* packed, size_t packed_len, const ui
     if (back[n + i] != 0xA5) { *err = "the unpack kernel wrote past the strip"; return false; }
   std::memcpy(out, back.data(), n);
   return true;
+}
+
+}  // namespace
+
+bool wire_unpack_device_probe(const uint8_t* packed, size_t packed_len, const uint32_t* table, size_t n, uint8_t* out,
+                              const char** err) {
+  return unpack_probe(packed, packed_len, table, nullptr, n, out, err);
+}
+
+bool wire_unpack2_device_probe(const uint8_t* packed, size_t packed_len, const uint32_t* table, const uint8_t* alpha,
+                               size_t n, uint8_t* out, const char** err) {
+  return unpack_probe(packed, packed_len, table, alpha, n, out, err);
 }
 
 }  // namespace tsg
