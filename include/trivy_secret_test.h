@@ -282,6 +282,15 @@ int tsg_test_plan_segments(const uint64_t* offsets, uint32_t nfiles, int residen
                            const tsg_segment_policy* pol, tsg_segment_info* out, uint32_t out_cap, uint32_t* nout,
                            uint64_t* rebased, size_t rebased_cap);
 
+/* The wire feeder's strip planner (csrc/wire_strips.h: plan_wire_strips, the
+ * code WireFeed cuts a segment into packer / copy strips with) on sizes alone:
+ * offsets[i], bytes[i] of strip i, i < *nout (*nout is set even when it
+ * exceeds cap, which fails).  first_segment 1: the scan's first segment, which
+ * gets the ramp of small strips where the rules allow one.  Tests only
+ * (tests/test_wire_strips.py). */
+int tsg_test_plan_wire_strips(uint64_t segment_bytes, uint64_t strip, int first_segment, int npackers,
+                              uint64_t* offsets, uint64_t* bytes, uint32_t cap, uint32_t* nout);
+
 /* Test hook: the engine's next n segment runs fail before their first
  * launch (as a failed device allocation would), so a test can check that a
  * failed call leaves nothing behind on the engine's pooled lanes.  Never used

@@ -9,6 +9,7 @@
 //       -o tools/wirepack_tool -lpthread
 //   tools/wirepack_tool rate [MiB per thread] [threads ...]   # pack GB/s of input against memcpy
 //   tools/wirepack_tool_asan check2      # the 6-bit codec (v2): the cases of tests/test_wirepack2.py
+//   tools/wirepack_tool_asan strips      # the strip planner (wire_strips.h) over the grid of tests/test_wire_strips.py
 //   tools/wirepack_tool rate2 FILE [MiB per thread] [threads ...]
 //       # v2 on FILE's bytes (repeated to fill 64 MiB strips): GB/s of input, packed / input with the strips'
 //       # heads, escaped share, blocks per mode, beside the 7-bit packer on the same bytes
@@ -23,6 +24,7 @@
 #include <thread>
 #include <vector>
 
+#include "wire_strips.h"
 #include "wirepack.h"
 
 using namespace tsg;
@@ -311,12 +313,72 @@ static int rate2(int argc, char** argv) {
   return 0;
 }
 
+// ---- the strip planner (wire_strips.h) over the grid of tests/test_wire_strips.py: random segment sizes in
+// [1, 2^33), the strip sizes the engine and its tests use, 0..16 packers; every plan is checked for exact cover in
+// order, aligned offsets, strip lengths, and the uniform cut where the ramp is off or does not fit
+
+static bool strips_case(uint64_t seg, uint64_t strip, bool first, int np) {
+  const std::vector<WireStrip> plan = plan_wire_strips(seg, strip, first, np);
+  uint64_t at = 0;
+  bool ok = !plan.empty();
+  for (size_t i = 0; ok && i < plan.size(); ++i) {
+    const WireStrip& s = plan[i];
+    ok = s.offset == at && s.bytes > 0 && s.bytes <= strip && (i + 1 == plan.size() || s.bytes % kWireBlock == 0) &&
+         (strip % kWireStripAlign != 0 || s.offset % kWireStripAlign == 0);
+    at += s.bytes;
+  }
+  ok = ok && at == seg;
+  const uint64_t m = static_cast<uint64_t>(kWireRampRounds) * np;
+  uint64_t need = kWireRampBack * (strip / kWireRampBackDiv);
+  for (uint64_t i = 0; i < m; ++i) need += wire_ramp_front(strip, i, m);
+  const bool ramp = first && np > 0 && strip >= kWireRampMinStrip && strip % kWireRampMinStrip == 0 && seg >= need;
+  const size_t nuniform = static_cast<size_t>((seg + strip - 1) / strip);
+  if (ok && !ramp) {
+    ok = plan.size() == nuniform;
+    for (size_t i = 0; ok && i < plan.size(); ++i) ok = plan[i].offset == i * strip;
+  }
+  if (ok && ramp) ok = plan.size() > nuniform && plan[0].bytes <= std::max(kWireStripAlign, strip / m) &&
+                       plan[m - 1].bytes == strip && plan.back().bytes <= strip / kWireRampBackDiv;
+  if (!ok) {
+    std::printf("FAIL strips: segment %llu strip %llu first %d packers %d\n", static_cast<unsigned long long>(seg),
+                static_cast<unsigned long long>(strip), first ? 1 : 0, np);
+    ++g_fail;
+  }
+  return ramp;
+}
+
+static int strips() {
+  const uint64_t sizes[] = {4096, 65536, 1ull << 20, 64ull << 20, kWireMaxStrip};
+  uint64_t x = 0x9E3779B97F4A7C15ull;
+  auto rnd = [&] { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return x; };
+  size_t cases = 0, ramped = 0;
+  for (uint64_t strip : sizes) {
+    for (int i = 0; i < 400; ++i) {
+      // log-uniform sizes; 4096-byte strips stay under 2^28 bytes (65536 strips)
+      const int bits = 1 + static_cast<int>(rnd() % (strip >= 65536 ? 33 : 28));
+      const uint64_t seg = std::max<uint64_t>(1, rnd() & ((1ull << bits) - 1));
+      const int np = static_cast<int>(rnd() % 17);
+      for (bool first : {true, false}) { ramped += strips_case(seg, strip, first, np); ++cases; }
+    }
+    for (int np : {1, 14, 16}) {
+      const uint64_t m = static_cast<uint64_t>(kWireRampRounds) * np;
+      uint64_t edge = kWireRampBack * (strip / kWireRampBackDiv);
+      for (uint64_t i = 0; i < m; ++i) edge += wire_ramp_front(strip, i, m);
+      for (uint64_t seg : {edge - 1, edge, edge + 1, edge + kWireStripAlign + 5, (uint64_t(1) << 33) - 1})
+        if (seg / strip < (1u << 21)) { ramped += strips_case(seg, strip, true, np); ++cases; }
+    }
+  }
+  std::printf("strips: %zu plans checked, %zu with a ramp, %d failed\n", cases, ramped, g_fail);
+  return g_fail ? 1 : 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 1 && std::strcmp(argv[1], "strips") == 0) return strips();
   if (argc > 1 && std::strcmp(argv[1], "check") == 0) return check();
   if (argc > 1 && std::strcmp(argv[1], "rate") == 0) return rate(argc, argv);
   if (argc > 1 && std::strcmp(argv[1], "check2") == 0) return check2();
   if (argc > 2 && std::strcmp(argv[1], "rate2") == 0) return rate2(argc, argv);
-  std::fprintf(stderr, "usage: %s check | rate [MiB per thread] [threads ...] | check2 | rate2 FILE [MiB per thread] "
+  std::fprintf(stderr, "usage: %s check | rate [MiB per thread] [threads ...] | check2 | strips | rate2 FILE [MiB per thread] "
                        "[threads ...]\n", argv[0]);
   return 2;
 }

@@ -151,6 +151,9 @@ SIGNATURES = [
                                                ctypes.c_int, ctypes.POINTER(TsgSegmentPolicy),
                                                ctypes.POINTER(TsgSegmentInfo), ctypes.c_uint32,
                                                ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p, ctypes.c_size_t]),
+    ("tsg_test_plan_wire_strips", ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                  ctypes.POINTER(ctypes.c_uint32)]),
     ("tsg_test_engine_footprint", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
                                                   ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
     ("tsg_test_keep_raw", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),

@@ -16,6 +16,7 @@
 #include "prefilter.h"
 #include "scanner.h"
 #include "segments.h"
+#include "wire_strips.h"
 #include "wirepack.h"
 #ifdef __HIPCC__
 #include "gather_dev.h"                 // (the engine's own translation unit: the gather kernels' launches)
@@ -296,6 +297,8 @@ class Engine {
   // ahead 160.9-161.1 (profiles/wirepack_c2.json).  Each packer holds a pinned
   // staging slot and a device twin of this size.
   uint64_t wire_strip_ = 64ull << 20;
+  bool wire_ramp_ = true;               // TSG_WIRE_RAMP=0: the uniform cut for the first segment too (wire_strips.h)
+  int wire_copy_streams_ = 2;           // TSG_WIRE_COPY_STREAMS: strip copies alternate over this many copy streams (1 or 2)
   std::mutex wire_mu_;
   std::condition_variable wire_cv_;
   std::vector<std::thread> wire_threads_;

@@ -1616,18 +1616,21 @@ struct LaneStreams {
   hipEvent_t up_begin[2] = {}, up_done[2] = {}; // upload ring slot: H2D start / done (copy stream)
   hipEvent_t anchor = nullptr;                   // TSG_HOST_PROFILE: start of a scan() on the copy stream
   // wire packing (WireFeed): the stream the unpack kernels run on; events of
-  // the raw strip copies in flight and of a segment's last copy
-  hipStream_t unpack = nullptr;
+  // the raw strip copies in flight and of a segment's last copy; the second
+  // copy stream strip copies alternate with `copy` on, and the event of its
+  // last copy of a segment
+  hipStream_t unpack = nullptr, copy2 = nullptr;
   hipEvent_t wire_raw_ev[4] = {};
   hipEvent_t wire_copies_done[2] = {};
+  hipEvent_t wire_copy2_done[2] = {};
   hipEvent_t gev[2] = {};                       // device-only scans: the gather kernels' start / end (compute stream)
   ~LaneStreams() {
     for (hipEvent_t* e : {&ev[0], &ev[1], &ev[2], &ev[3], &ev_sync, &up_begin[0], &up_begin[1], &up_done[0], &up_done[1],
                           &gev[0], &gev[1],
                           &anchor, &wire_raw_ev[0], &wire_raw_ev[1], &wire_raw_ev[2], &wire_raw_ev[3],
-                          &wire_copies_done[0], &wire_copies_done[1]})
+                          &wire_copies_done[0], &wire_copies_done[1], &wire_copy2_done[0], &wire_copy2_done[1]})
       if (*e) (void)hipEventDestroy(*e);
-    for (hipStream_t st : {unpack, compute, copy}) if (st) (void)hipStreamDestroy(st);
+    for (hipStream_t st : {unpack, copy2, compute, copy}) if (st) (void)hipStreamDestroy(st);
   }
 };
 
@@ -1778,9 +1781,11 @@ void Lane::free_wire() {
 // the lane).
 bool Lane::ensure_wire(size_t nslots, size_t cap, std::string* err) {
   if (!unpack) HIP_OK(hipStreamCreateWithFlags(&unpack, hipStreamNonBlocking));
+  if (!copy2) HIP_OK(hipStreamCreateWithFlags(&copy2, hipStreamNonBlocking));
   const unsigned evf = hipEventBlockingSync | hipEventDisableTiming;
   for (auto& e : wire_raw_ev) if (!e) HIP_OK(hipEventCreateWithFlags(&e, evf));
   for (auto& e : wire_copies_done) if (!e) HIP_OK(hipEventCreateWithFlags(&e, evf));
+  for (auto& e : wire_copy2_done) if (!e) HIP_OK(hipEventCreateWithFlags(&e, evf));
   if (wire.size() >= nslots && wire_cap >= cap) return true;
   free_wire();
   wire.resize(nslots);
@@ -1798,6 +1803,7 @@ Lane::~Lane() {
   hipSetDevice(device);
   if (compute) hipStreamSynchronize(compute);
   if (copy) hipStreamSynchronize(copy);
+  if (copy2) hipStreamSynchronize(copy2);
   if (unpack) hipStreamSynchronize(unpack);
   free_wire();
   // (then the buffers, then ~LaneStreams)
@@ -2077,6 +2083,10 @@ std::unique_ptr<Engine> Engine::create(std::shared_ptr<const Ruleset> rs, const 
   if (const char* c = std::getenv("TSG_WIRE_STRIP_BYTES")) {
     const long long v = std::atoll(c);
     if (v >= kWireBlock) e->wire_strip_ = std::min<uint64_t>(static_cast<uint64_t>(v) / kWireBlock * kWireBlock, kWireMaxStrip);
+  }
+  if (const char* c = std::getenv("TSG_WIRE_RAMP")) e->wire_ramp_ = std::atoi(c) != 0;
+  if (const char* c = std::getenv("TSG_WIRE_COPY_STREAMS")) {
+    if (std::strcmp(c, "1") == 0 || std::strcmp(c, "2") == 0) e->wire_copy_streams_ = c[0] - '0';   // (anything else: ignored)
   }
   if (e->host_profile_) g_scan_prof_on.store(true, std::memory_order_relaxed);
   env_int("TSG_GATHER_CAP", 256, INT64_MAX, &e->gather_cap_);   // (from 256 bytes: tests force the capacity retry)
@@ -2958,12 +2968,22 @@ bool Engine::prefilter_only(const BatchInput& in, std::vector<std::vector<std::v
 // restored in the ring by that codec's unpack kernel before K1 reads them.  The
 // engine's packer threads claim strips from the front of the feeder's segment
 // (then of the next one) and pack them into the lane's pinned staging slots; the scan's feeder thread
-// owns the copy stream, keeps kWireCopiesAhead strip copies queued and, when
+// owns the copy streams, keeps kWireCopiesAhead strip copies queued and, when
 // no packed strip is ready, claims a strip from the back of the segment and
 // sends it as it is from the caller's memory, so packing never makes the link
-// wait.  Unpack kernels run on the lane's third stream behind their copy's
-// event; up_done[slot] is recorded there once every copy of the segment and
-// every unpack is queued before it.
+// wait.  Where a segment's strips lie is its plan (wire_strips.h: the first
+// segment's starts and ends with small strips).  Strip copies go to the lane's
+// two copy streams in turn (TSG_WIRE_COPY_STREAMS=1: all to the first): two
+// copies then run at a time, each at half the link's rate, and the ~15 us the
+// link idles between two copies of one stream is paid once per pair (copy
+// traces in profiles/wirefeed_*); strips are independent, each has its own
+// events.  Everything else of a segment -- up_begin, the
+// offsets, the bytes past the end, wire_copies_done -- is on the first stream:
+// the second waits on up_begin before the segment's first copy, and the first
+// on the second's last copy before wire_copies_done.  Unpack kernels run on
+// the lane's unpack stream behind their copy's event; up_done[slot] is
+// recorded there once every copy of the segment and every unpack is queued
+// before it.
 constexpr size_t kWireCopiesAhead = 3;
 
 void wire_unpack_launch(const uint8_t* land, uint32_t tab_bytes, uint8_t* dst, uint32_t n, hipStream_t stream);
@@ -2980,10 +3000,12 @@ struct WireFeed {
   bool force = false;                  // the feeder waits for the packers instead of sending raw strips
   bool v2 = false;                     // the 6-bit codec (wirepack.h); else the 7-bit one
   int npackers = 0;
+  int ncopy = 1;                       // copy streams the strip copies alternate over
   bool timeline = false;
+  std::vector<std::vector<WireStrip>> plan;   // per segment: its strips (wire_strips.h); fixed once the feed starts
   std::mutex mu;                       // guards everything below
   std::condition_variable cv;
-  // per segment: strips [front, back) are unclaimed.  Packers take the
+  // per segment: strips [front, back) of its plan are unclaimed.  Packers take the
   // front of the segment the feeder is on (feed_seg) and, once that one is
   // claimed out, of the next, so the link does not wait for the first packed
   // strips of a new segment (staging is not the ring: only the feeder, which
@@ -3058,9 +3080,8 @@ void WireFeed::pack_loop() {
     --nfree;
     const size_t sgi = static_cast<size_t>(pack_seg());
     const uint32_t s = span[sgi].front++;
-    const uint64_t o = static_cast<uint64_t>(s) * strip;
-    const uint8_t* p = segs[sgi].src + o;
-    const size_t n = static_cast<size_t>(std::min<uint64_t>(strip, segs[sgi].bytes - o));
+    const uint8_t* p = segs[sgi].src + plan[sgi][s].offset;
+    const size_t n = static_cast<size_t>(plan[sgi][s].bytes);
     lk.unlock();
     auto t0 = std::chrono::steady_clock::now();
     Lane::WireSlot& w = ln->wire[id];
@@ -3122,12 +3143,14 @@ bool WireFeed::feed_segment(size_t si, std::string* err) {
   std::memcpy(ln->h_off_pin[slot].p, sg.offsets, (sg.nfiles + 1) * sizeof(uint64_t));
   HIP_OK(hipMemcpyAsync(ln->off_slot[slot].p, ln->h_off_pin[slot].p, (sg.nfiles + 1) * sizeof(uint64_t),
                         hipMemcpyHostToDevice, ln->copy));
-  const uint32_t ns = static_cast<uint32_t>((sg.bytes + strip - 1) / strip);
+  const uint32_t ns = static_cast<uint32_t>(plan[si].size());
   {
     std::lock_guard<std::mutex> lk(mu);
     feed_seg = si;
   }
   cv.notify_all();
+  const hipStream_t cs[2] = {ln->copy, ncopy > 1 ? ln->copy2 : ln->copy};
+  if (ncopy > 1) HIP_OK(hipStreamWaitEvent(ln->copy2, ln->up_begin[slot], 0));
   uint64_t sent = 0;
   uint32_t npacked = 0, nraw = 0;
   Wire2Stats modes;
@@ -3161,8 +3184,9 @@ bool WireFeed::feed_segment(size_t si, std::string* err) {
       HIP_OK(hipEventSynchronize(!copies.empty() ? copies.front().ev : unpacks.front().ev));
       continue;
     }
-    const uint64_t o = static_cast<uint64_t>(s) * strip;
-    const size_t n = static_cast<size_t>(std::min<uint64_t>(strip, sg.bytes - o));
+    const uint64_t o = plan[si][s].offset;
+    const size_t n = static_cast<size_t>(plan[si][s].bytes);
+    const hipStream_t cst = cs[issued & 1];
     if (id >= 0 && wire_len >= n) {
       // nothing gained (a strip of non-ASCII blocks): it goes as it is
       std::lock_guard<std::mutex> lk(mu);
@@ -3172,16 +3196,16 @@ bool WireFeed::feed_segment(size_t si, std::string* err) {
       cv.notify_all();
     }
     if (id < 0) {
-      HIP_OK(hipMemcpyAsync(ln->ring[slot].p + o, sg.src + o, n, hipMemcpyHostToDevice, ln->copy));
+      HIP_OK(hipMemcpyAsync(ln->ring[slot].p + o, sg.src + o, n, hipMemcpyHostToDevice, cst));
       hipEvent_t ev = ln->wire_raw_ev[raw_i++ & 3];
-      HIP_OK(hipEventRecord(ev, ln->copy));
+      HIP_OK(hipEventRecord(ev, cst));
       copies.push_back({ev, -1});
       sent += n;
       ++nraw;
     } else {
       Lane::WireSlot& w = ln->wire[id];
-      HIP_OK(hipMemcpyAsync(w.d, w.h, wire_len, hipMemcpyHostToDevice, ln->copy));
-      HIP_OK(hipEventRecord(w.copied, ln->copy));
+      HIP_OK(hipMemcpyAsync(w.d, w.h, wire_len, hipMemcpyHostToDevice, cst));
+      HIP_OK(hipEventRecord(w.copied, cst));
       HIP_OK(hipStreamWaitEvent(ln->unpack, w.copied, 0));
       if (v2) {
         wire_unpack2_launch(w.d, static_cast<uint32_t>(wire_table_bytes(n)), static_cast<uint32_t>(wire2_alpha_bytes(n)),
@@ -3204,6 +3228,10 @@ bool WireFeed::feed_segment(size_t si, std::string* err) {
       }
     }
     ++issued;
+  }
+  if (ncopy > 1) {
+    HIP_OK(hipEventRecord(ln->wire_copy2_done[slot], ln->copy2));
+    HIP_OK(hipStreamWaitEvent(ln->copy, ln->wire_copy2_done[slot], 0));
   }
   HIP_OK(hipMemsetAsync(ln->ring[slot].p + sg.bytes, 0, 64, ln->copy));   // K1 reads 16-B words past the end
   HIP_OK(hipEventRecord(ln->wire_copies_done[slot], ln->copy));
@@ -3254,6 +3282,7 @@ void WireFeed::feed_loop() {
     // failed or stopped early: nothing of this scan stays queued on the
     // feeder's streams, and no copy reads the caller's memory any more
     hipStreamSynchronize(ln->copy);
+    if (ln->copy2) hipStreamSynchronize(ln->copy2);
     hipStreamSynchronize(ln->unpack);
   }
   {
@@ -3277,12 +3306,14 @@ bool WireFeed::start(Engine& eng, Lane* ln, int device, const std::vector<Segmen
   f->force = eng.wire_mode_ == 2;
   f->v2 = eng.wire_codec_ == 2;
   f->npackers = np;
+  f->ncopy = eng.wire_copy_streams_;
   f->timeline = eng.host_profile_;
   f->slots.resize(nslots);
   f->nfree = static_cast<int>(nslots);
   for (const Segment& sg : segs) {
     f->segs.push_back({sg.in.h_data, sg.bytes, sg.in.offsets, sg.in.nfiles});
-    f->span.push_back({0, static_cast<uint32_t>((sg.bytes + f->strip - 1) / f->strip)});
+    f->plan.push_back(plan_wire_strips(sg.bytes, f->strip, eng.wire_ramp_ && f->plan.empty(), np));
+    f->span.push_back({0, static_cast<uint32_t>(f->plan.back().size())});
   }
   {
     std::lock_guard<std::mutex> lk(eng.wire_mu_);
@@ -4163,7 +4194,12 @@ struct SegmentDriver {
   void teardown(bool ok, std::chrono::steady_clock::time_point tb) {
     if (wf) wf->wind_down(&dst);
     if (ln) {
-      if (!ok) { hipStreamSynchronize(ln->copy); hipStreamSynchronize(ln->compute); if (ln->unpack) hipStreamSynchronize(ln->unpack); }
+      if (!ok) {
+        hipStreamSynchronize(ln->copy);
+        if (ln->copy2) hipStreamSynchronize(ln->copy2);
+        hipStreamSynchronize(ln->compute);
+        if (ln->unpack) hipStreamSynchronize(ln->unpack);
+      }
       ln->pool_idle = nullptr;                   // (the flag is this scan's)
       eng.release_lane(*dt, ln);
     }

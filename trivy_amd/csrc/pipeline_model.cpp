@@ -25,6 +25,7 @@
 #include "segments.h"
 #include "trivy_secret.h"
 #include "trivy_secret_test.h"
+#include "wire_strips.h"
 
 namespace tsg {
 int capi_fail(int code, const std::string& m);   // capi.cpp: sets tsg_last_error
@@ -185,5 +186,23 @@ extern "C" int tsg_test_plan_segments(const uint64_t* offsets, uint32_t nfiles, 
     return TSG_OK;
   } catch (const std::exception& x) {
     return capi_fail(TSG_ERR_INTERNAL, std::string("internal error: ") + x.what());
+  }
+}
+
+extern "C" int tsg_test_plan_wire_strips(uint64_t segment_bytes, uint64_t strip, int first_segment, int npackers,
+                                         uint64_t* offsets, uint64_t* bytes, uint32_t cap, uint32_t* nout) {
+  using namespace tsg;
+  if (!nout || strip == 0 || (cap && (!offsets || !bytes))) return capi_fail(TSG_ERR_INVALID, "bad argument");
+  try {
+    const std::vector<WireStrip> plan = plan_wire_strips(segment_bytes, strip, first_segment != 0, npackers);
+    *nout = static_cast<uint32_t>(plan.size());
+    if (plan.size() > cap) return capi_fail(TSG_ERR_INVALID, "more strips than cap");
+    for (size_t i = 0; i < plan.size(); ++i) {
+      offsets[i] = plan[i].offset;
+      bytes[i] = plan[i].bytes;
+    }
+    return TSG_OK;
+  } catch (const std::bad_alloc&) {
+    return capi_fail(TSG_ERR_INTERNAL, "out of memory");
   }
 }
