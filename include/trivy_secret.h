@@ -107,6 +107,7 @@ typedef struct tsg_stats {
   uint64_t blocks_7bit;
   uint64_t blocks_raw;
   uint64_t escaped_bytes;
+  uint64_t blocks_split;  /* blocks sent in the 6-bit codec's split mode; their escaped bytes count above */
 } tsg_stats;
 
 const char* tsg_last_error(void);

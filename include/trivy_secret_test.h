@@ -322,6 +322,15 @@ int tsg_test_wire_pack2(const uint8_t* src, size_t n, int path, uint8_t* packed,
                         uint8_t* alpha, size_t* packed_len, int* path_used, uint64_t* counts, uint8_t* back);
 int tsg_test_wire_unpack2_device(const uint8_t* packed, size_t packed_len, const uint32_t* table, const uint8_t* alpha,
                                  size_t n, uint8_t* out);
+/* tsg_test_wire_pack2 with split blocks allowed (a table entry with bits 31
+ * and 30 both set).  *vbmi2 (may be NULL): whether path 3 packs them with
+ * AVX-512 VBMI2 on this CPU.  counts: 5 values, the fifth the split blocks;
+ * the escaped bytes count those of 6-bit and split blocks.  The device hook
+ * is the v2 one under the format's other name. */
+int tsg_test_wire_pack3(const uint8_t* src, size_t n, int path, uint8_t* packed, size_t packed_cap, uint32_t* table,
+                        uint8_t* alpha, size_t* packed_len, int* path_used, int* vbmi2, uint64_t* counts, uint8_t* back);
+int tsg_test_wire_unpack3_device(const uint8_t* packed, size_t packed_len, const uint32_t* table, const uint8_t* alpha,
+                                 size_t n, uint8_t* out);
 
 /* The same two pipelines with the CPU model of the GPU passes as the scan
  * stage (tsg_scan_table_model's); tests only, never the product path. */

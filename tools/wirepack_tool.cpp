@@ -13,6 +13,8 @@
 //   tools/wirepack_tool rate2 FILE [MiB per thread] [threads ...]
 //       # v2 on FILE's bytes (repeated to fill 64 MiB strips): GB/s of input, packed / input with the strips'
 //       # heads, escaped share, blocks per mode, beside the 7-bit packer on the same bytes
+//   tools/wirepack_tool_asan check3      # check2's cases with split blocks allowed
+//   tools/wirepack_tool rate3 FILE [MiB per thread] [threads ...]    # rate2 with split blocks allowed
 //       # (WIREPACK_PATH=1|2|3 in the environment: the scalar, AVX2 or VBMI path instead of the CPU's best)
 #include <algorithm>
 #include <chrono>
@@ -148,6 +150,9 @@ static const char* path_name(int p) { return p == kWireVbmi ? "vbmi" : p == kWir
 
 // as one_case: every path from an exact-size source into exact-size buffers, the round trip from exact-size
 // packed bytes, and the format's invariants; the exact bytes are the Python model's to predict
+static bool g_split = false;   // check3: the same cases with split blocks allowed
+static unsigned long long g_split_blocks = 0;
+
 static void one_case2(const char* name, const std::vector<uint8_t>& data, size_t mis) {
   const size_t n = data.size();
   std::unique_ptr<uint8_t[]> raw(new uint8_t[n + mis]);
@@ -160,15 +165,16 @@ static void one_case2(const char* name, const std::vector<uint8_t>& data, size_t
     tab[k].assign(wire_blocks(n), 0);
     alpha[k].assign(wire2_alpha_bytes(n), 0xEE);
     Wire2Stats st;
-    const size_t pl = wire_pack2(src, n, dst.get(), tab[k].data(), alpha[k].data(), k + 1, &st);
+    const size_t pl = wire_pack2(src, n, dst.get(), tab[k].data(), alpha[k].data(), k + 1, &st, g_split);
     packed[k].assign(dst.get(), dst.get() + pl);
+    g_split_blocks += st.blocks_split;
     std::unique_ptr<uint8_t[]> back(new uint8_t[n]);
     wire_unpack2(packed[k].data(), tab[k].data(), alpha[k].data(), n, back.get());
     if (n && std::memcmp(back.get(), src, n) != 0) { std::printf("FAIL %s: round trip (path %d)\n", name, k + 1); ++g_fail; }
     if (pl > n + 15) { std::printf("FAIL %s: packed size %zu (path %d)\n", name, pl, k + 1); ++g_fail; }
-    if (st.blocks6 + st.blocks7 + st.blocks_raw != wire_blocks(n)) { std::printf("FAIL %s: block counts\n", name); ++g_fail; }
+    if (st.blocks6 + st.blocks7 + st.blocks_raw + st.blocks_split != wire_blocks(n) || (!g_split && st.blocks_split)) { std::printf("FAIL %s: block counts\n", name); ++g_fail; }
     for (uint32_t t : tab[k])
-      if ((t & 15u) || ((t & kWireRawBit) && (t & kWire6Bit))) { std::printf("FAIL %s: table entry %08x\n", name, t); ++g_fail; }
+      if ((t & 15u) || (!g_split && (t & kWireRawBit) && (t & kWire6Bit))) { std::printf("FAIL %s: table entry %08x\n", name, t); ++g_fail; }
   }
   for (int k = 1; k < 3; ++k)
     if (packed[0] != packed[k] || tab[0] != tab[k] || alpha[0] != alpha[k]) {
@@ -187,9 +193,21 @@ static std::vector<uint8_t> words(size_t n, uint32_t seed) {
   return v;
 }
 
+// 63 values of which a few are far more frequent than the rest: blocks of it go split where that is allowed
+static std::vector<uint8_t> skewed(size_t n, uint32_t seed) {
+  static const char vals[] = "etaoin shrdlucmfwypvbgkqjxzETAOINSHRDLUCMFWYPVBGKQJXZ0123456789_";
+  std::vector<uint8_t> v(n);
+  for (size_t i = 0; i < n; ++i) {
+    seed = seed * 1664525u + 1013904223u;
+    const uint32_t a = (seed >> 8) % 63, b = (seed >> 20) % 63;
+    v[i] = static_cast<uint8_t>(vals[a * b / 63]);
+  }
+  return v;
+}
+
 static int check2() {
   const size_t B = kWireBlock, R = kWire2Region;
-  const size_t lens[] = {0, 1, 3, 4, 5, 15, 16, 17, 63, 64, 65, B - 1, B, B + 1, 2 * B + 5};
+  const size_t lens[] = {0, 1, 3, 4, 5, 15, 16, 17, 63, 64, 65, 100, 1000, 1001, B - 1, B, B + 1, 2 * B + 5, 3 * B + 77};
   char name[64];
   for (size_t n : lens)
     for (size_t mis : {size_t(0), size_t(1), size_t(3), size_t(13)}) {
@@ -197,6 +215,8 @@ static int check2() {
       one_case2(name, words(n, 7 + static_cast<uint32_t>(n)), mis);
       std::snprintf(name, sizeof name, "noise len %zu mis %zu", n, mis);
       one_case2(name, text(n, 9 + static_cast<uint32_t>(n)), mis);
+      std::snprintf(name, sizeof name, "skewed len %zu mis %zu", n, mis);
+      one_case2(name, skewed(n, 13 + static_cast<uint32_t>(n)), mis);
     }
   const uint8_t vals[] = {0x00, 0x7F, 0x80, 0xFF};
   const size_t strip = R + 4 * B;
@@ -239,8 +259,20 @@ static int check2() {
     d.insert(d.end(), x.begin(), x.end());
     one_case2("two regions", d, 3);
   }
-  std::printf("wirepack check2: %s (AVX2 %s, VBMI %s)\n", g_fail ? "FAILED" : "ok",
-              wire_have_avx2() ? "yes" : "no: scalar in its place", wire_have_vbmi() ? "yes" : "no: the path below in its place");
+  // hot and warm values in turn, by byte and by runs that end at the 1024-byte edges; every 16th byte escaping
+  {
+    std::vector<uint8_t> d = words(3 * B + 333, 31);
+    const uint8_t hot = d[0], warm = '%';
+    for (size_t i = 0; i < B; ++i) d[i] = i % 2 ? hot : static_cast<uint8_t>('a' + i / 2 % 26);
+    for (size_t i = B; i < 2 * B; ++i) d[i] = (i / 1024) % 2 ? hot : static_cast<uint8_t>('A' + i % 26);
+    for (size_t i = 2 * B; i < 3 * B; i += 16) d[i + 1] = warm;
+    for (size_t i = 2 * B + 32; i < 2 * B + 48; ++i) d[i] = 0x80 + static_cast<uint8_t>(i % 16);
+    one_case2("hot and warm patterns", d, 5);
+  }
+  std::printf("split blocks written: %llu\n", g_split_blocks);
+  std::printf("wirepack check%s: %s (AVX2 %s, VBMI %s, VBMI2 %s)\n", g_split ? "3" : "2", g_fail ? "FAILED" : "ok",
+              wire_have_avx2() ? "yes" : "no: scalar in its place", wire_have_vbmi() ? "yes" : "no: the path below in its place",
+              wire_have_vbmi2() ? "yes" : "no");
   return g_fail ? 1 : 0;
 }
 
@@ -285,7 +317,7 @@ static int rate2(int argc, char** argv) {
             std::vector<uint32_t> tab(wire_blocks(bytes));
             std::vector<uint8_t> alpha(wire2_alpha_bytes(bytes));
             for (int r = 0; r < reps; ++r) {
-              if (v2) pl2[t] = wire_pack2(src[t].data(), bytes, dst[t].data(), tab.data(), alpha.data(), path, &st[t]);
+              if (v2) pl2[t] = wire_pack2(src[t].data(), bytes, dst[t].data(), tab.data(), alpha.data(), path, &st[t], g_split);
               else pl1[t] = wire_pack(src[t].data(), bytes, dst[t].data(), tab.data(), kWireAuto);
             }
           });
@@ -297,16 +329,18 @@ static int rate2(int argc, char** argv) {
     double sent2 = 0, sent1 = 0;
     for (int t = 0; t < nt; ++t) {
       a.blocks6 += st[t].blocks6; a.blocks7 += st[t].blocks7; a.blocks_raw += st[t].blocks_raw; a.escaped += st[t].escaped;
+      a.blocks_split += st[t].blocks_split;
       sent2 += static_cast<double>(wire_table_bytes(bytes) + wire2_alpha_bytes(bytes) + pl2[t]);
       sent1 += static_cast<double>(wire_table_bytes(bytes) + pl1[t]);
     }
     const double in = static_cast<double>(bytes) * nt;
     std::printf("{\"file\": \"%s\", \"file_mb\": %.1f, \"threads\": %d, \"mib_per_thread\": %zu, \"path\": \"%s\", "
                 "\"pack2_gbps\": %.2f, \"ratio2\": %.4f, \"escaped_share\": %.5f, \"blocks_6bit\": %llu, "
-                "\"blocks_7bit\": %llu, \"blocks_raw\": %llu, \"pack7_gbps\": %.2f, \"ratio7\": %.4f}\n",
+                "\"blocks_7bit\": %llu, \"blocks_raw\": %llu, \"blocks_split\": %llu, \"vbmi2\": %s, \"pack7_gbps\": %.2f, \"ratio7\": %.4f}\n",
                 argv[2], file.size() / 1e6, nt, bytes >> 20, path_name(wire2_path(path)), gbps[1], sent2 / in,
                 static_cast<double>(a.escaped) / in, static_cast<unsigned long long>(a.blocks6),
-                static_cast<unsigned long long>(a.blocks7), static_cast<unsigned long long>(a.blocks_raw), gbps[0],
+                static_cast<unsigned long long>(a.blocks7), static_cast<unsigned long long>(a.blocks_raw),
+                static_cast<unsigned long long>(a.blocks_split), wire_have_vbmi2() ? "true" : "false", gbps[0],
                 sent1 / in);
     std::fflush(stdout);
   }
@@ -378,7 +412,9 @@ int main(int argc, char** argv) {
   if (argc > 1 && std::strcmp(argv[1], "rate") == 0) return rate(argc, argv);
   if (argc > 1 && std::strcmp(argv[1], "check2") == 0) return check2();
   if (argc > 2 && std::strcmp(argv[1], "rate2") == 0) return rate2(argc, argv);
-  std::fprintf(stderr, "usage: %s check | rate [MiB per thread] [threads ...] | check2 | strips | rate2 FILE [MiB per thread] "
-                       "[threads ...]\n", argv[0]);
+  if (argc > 1 && std::strcmp(argv[1], "check3") == 0) { g_split = true; return check2(); }
+  if (argc > 2 && std::strcmp(argv[1], "rate3") == 0) { g_split = true; return rate2(argc, argv); }
+  std::fprintf(stderr, "usage: %s check | rate [MiB per thread] [threads ...] | check2 | check3 | strips | "
+                       "rate2 FILE [MiB per thread] [threads ...] | rate3 FILE ...\n", argv[0]);
   return 2;
 }

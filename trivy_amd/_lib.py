@@ -63,7 +63,7 @@ class TsgStats(ctypes.Structure):
                 ("wire_bytes", ctypes.c_uint64), ("packed_strips", ctypes.c_uint32), ("raw_strips", ctypes.c_uint32),
                 ("pack_ms", ctypes.c_double),
                 ("blocks_6bit", ctypes.c_uint64), ("blocks_7bit", ctypes.c_uint64), ("blocks_raw", ctypes.c_uint64),
-                ("escaped_bytes", ctypes.c_uint64)]
+                ("escaped_bytes", ctypes.c_uint64), ("blocks_split", ctypes.c_uint64)]
 
 
 # (name, restype, argtypes) for every entry point declared in include/trivy_secret.h
@@ -170,6 +170,12 @@ SIGNATURES = [
                                             ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int),
                                             ctypes.c_void_p, ctypes.c_void_p]),
     ("tsg_test_wire_unpack2_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    ("tsg_test_wire_pack3", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p,
+                                            ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int),
+                                            ctypes.POINTER(ctypes.c_int), ctypes.c_void_p, ctypes.c_void_p]),
+    ("tsg_test_wire_unpack3_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                                      ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     ("tsg_scan_host_reference", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                                 c_char_pp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,

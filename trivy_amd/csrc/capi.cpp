@@ -488,6 +488,7 @@ int tsg_result_stats(const tsg_result* r, tsg_stats* out) {
   out->pack_ms = s.pack_ms;
   out->blocks_6bit = s.blocks_6bit; out->blocks_7bit = s.blocks_7bit; out->blocks_raw = s.blocks_raw;
   out->escaped_bytes = s.escaped_bytes;
+  out->blocks_split = s.blocks_split;
   return TSG_OK;
   TSG_API_CATCH
 }
@@ -1088,8 +1089,9 @@ int tsg_test_wire_unpack_device(const uint8_t* packed, size_t packed_len, const 
   TSG_API_CATCH
 }
 
-int tsg_test_wire_pack2(const uint8_t* src, size_t n, int path, uint8_t* packed, size_t packed_cap, uint32_t* table,
-                        uint8_t* alpha, size_t* packed_len, int* path_used, uint64_t* counts, uint8_t* back) {
+static int test_wire_pack2(const uint8_t* src, size_t n, int path, bool split, uint8_t* packed, size_t packed_cap,
+                           uint32_t* table, uint8_t* alpha, size_t* packed_len, int* path_used, uint64_t* counts,
+                           uint8_t* back) {
   TSG_API_TRY
   if ((!src && n) || !table || !alpha || !packed_len || (!packed && packed_cap)) return fail(TSG_ERR_INVALID, "NULL argument");
   if (path < 0 || path > 3 || n > kWireMaxStrip) return fail(TSG_ERR_INVALID, "path or length out of range");
@@ -1097,10 +1099,11 @@ int tsg_test_wire_pack2(const uint8_t* src, size_t n, int path, uint8_t* packed,
   std::vector<uint32_t> tab(wire_blocks(n) + 1);
   std::vector<uint8_t> al(wire2_alpha_bytes(n) + 1);
   Wire2Stats st;
-  const size_t pl = wire_pack2(src, n, buf.data(), tab.data(), al.data(), path, &st);
+  const size_t pl = wire_pack2(src, n, buf.data(), tab.data(), al.data(), path, &st, split);
   *packed_len = pl;
   if (path_used) *path_used = wire2_path(path);
   if (counts) { counts[0] = st.blocks6; counts[1] = st.blocks7; counts[2] = st.blocks_raw; counts[3] = st.escaped; }
+  if (counts && split) counts[4] = st.blocks_split;
   if (pl > packed_cap) return fail(TSG_ERR_INVALID, "packed_cap is too small");
   if (pl) memcpy(packed, buf.data(), pl);
   memcpy(table, tab.data(), wire_blocks(n) * sizeof(uint32_t));
@@ -1114,6 +1117,17 @@ int tsg_test_wire_pack2(const uint8_t* src, size_t n, int path, uint8_t* packed,
   TSG_API_CATCH
 }
 
+int tsg_test_wire_pack2(const uint8_t* src, size_t n, int path, uint8_t* packed, size_t packed_cap, uint32_t* table,
+                        uint8_t* alpha, size_t* packed_len, int* path_used, uint64_t* counts, uint8_t* back) {
+  return test_wire_pack2(src, n, path, false, packed, packed_cap, table, alpha, packed_len, path_used, counts, back);
+}
+
+int tsg_test_wire_pack3(const uint8_t* src, size_t n, int path, uint8_t* packed, size_t packed_cap, uint32_t* table,
+                        uint8_t* alpha, size_t* packed_len, int* path_used, int* vbmi2, uint64_t* counts, uint8_t* back) {
+  if (vbmi2) *vbmi2 = wire_have_vbmi2() ? 1 : 0;
+  return test_wire_pack2(src, n, path, true, packed, packed_cap, table, alpha, packed_len, path_used, counts, back);
+}
+
 int tsg_test_wire_unpack2_device(const uint8_t* packed, size_t packed_len, const uint32_t* table, const uint8_t* alpha,
                                  size_t n, uint8_t* out) {
   TSG_API_TRY
@@ -1122,6 +1136,12 @@ int tsg_test_wire_unpack2_device(const uint8_t* packed, size_t packed_len, const
   if (!wire_unpack2_device_probe(packed, packed_len, table, alpha, n, out, &msg)) return fail(TSG_ERR_INTERNAL, msg);
   return TSG_OK;
   TSG_API_CATCH
+}
+
+int tsg_test_wire_unpack3_device(const uint8_t* packed, size_t packed_len, const uint32_t* table, const uint8_t* alpha,
+                                 size_t n, uint8_t* out) {
+  // (one kernel restores every mode of the format)
+  return tsg_test_wire_unpack2_device(packed, packed_len, table, alpha, n, out);
 }
 
 static std::string cstr(const char* p) { return p ? std::string(p) : std::string(); }

@@ -44,7 +44,7 @@ struct ScanStats {
   double pack_ms = 0;
   // blocks of the strips sent packed by the mode they crossed in, and the
   // bytes the 6-bit blocks escaped
-  uint64_t blocks_6bit = 0, blocks_7bit = 0, blocks_raw = 0, escaped_bytes = 0;
+  uint64_t blocks_6bit = 0, blocks_7bit = 0, blocks_raw = 0, escaped_bytes = 0, blocks_split = 0;
   // device-only scans (gather.h): files, bytes and runs the GPU gathered for
   // the confirmer, the gather kernels' time, copy launches repeated with a
   // larger buffer
@@ -284,11 +284,15 @@ class Engine {
   bool file_index_ = true;              // K1 range starts' files from a per-64-KiB index (TSG_K1_FILE_INDEX)
   // Wire packing of uploaded batches (wirepack.h; TSG_WIRE_PACK 0 = off, 1 =
   // packers race the link, force = every strip waits for a packer, both with
-  // the 7-bit codec; 2 and force2 = the same with the 6-bit codec).  The
+  // the 7-bit codec; 2 and force2 = the same with the 6-bit codec; 3 and
+  // force3 = the 6-bit codec with split blocks allowed.  Unset: 2, with split
+  // blocks where the CPU packs them with VBMI2 and the scan uploads at least
+  // kWireDenseMinBytes -- a smaller one is over before the packers are ahead).  The
   // packer threads belong to the engine: started on the first eligible scan,
   // parked on wire_cv_ between scans, serving one scan at a time (wire_job_).
   int wire_mode_ = 0;                   // 0 off, 1 race, 2 force
   int wire_codec_ = 1;                  // 1 = 7-bit, 2 = 6-bit codes with escapes
+  int wire_split_ = 0;                  // split blocks: 0 = never, 1 = allowed, -1 = by the rule for an unset TSG_WIRE_PACK
   int wire_threads_n_ = -1;             // TSG_WIRE_PACK_THREADS; -1 = the engine's threads - 2, at most 16
   // bytes per strip (TSG_WIRE_STRIP_BYTES, a multiple of 4096).  Config 2, 14
   // packers: 4 MiB 198.7 ms per step, 8 MiB 179.2, 16 MiB 169.9-170.2, 32 MiB

@@ -1601,6 +1601,10 @@ struct StageIn {
 };
 constexpr uint64_t kDirectStageBytes = 1u << 20;     // batches up to this size (and pinned) are staged by the prologue
 constexpr const char* kWirePackDefault = "2";  // TSG_WIRE_PACK unset: packers race the link with the 6-bit codec (wirepack.h)
+// ... and whether its packers may write split blocks (Engine::wire_split_; -1:
+// where VBMI2 packs them, in scans that upload kWireDenseMinBytes or more)
+constexpr int kWireSplitDefault = -1;
+constexpr uint64_t kWireDenseMinBytes = 1ull << 30;
 
 // One in-flight call's resources on one device: its own streams (compute +
 // copy), timing events, the two-slot upload ring and every per-batch scratch
@@ -2033,6 +2037,7 @@ void add_stats(ScanStats* a, const ScanStats& s) {
   a->pack_ms += s.pack_ms;
   a->blocks_6bit += s.blocks_6bit; a->blocks_7bit += s.blocks_7bit; a->blocks_raw += s.blocks_raw;
   a->escaped_bytes += s.escaped_bytes;
+  a->blocks_split += s.blocks_split;
   a->gather_bytes += s.gather_bytes; a->gather_runs += s.gather_runs; a->gather_ms += s.gather_ms;
   a->gather_retries += s.gather_retries;
 }
@@ -2075,8 +2080,10 @@ std::unique_ptr<Engine> Engine::create(std::shared_ptr<const Ruleset> rs, const 
   {
     const char* c = std::getenv("TSG_WIRE_PACK");
     if (!c) c = kWirePackDefault;
-    const bool v2 = std::strcmp(c, "force2") == 0 || std::strcmp(c, "2") == 0;
+    const bool v3 = std::strcmp(c, "force3") == 0 || std::strcmp(c, "3") == 0;
+    const bool v2 = v3 || std::strcmp(c, "force2") == 0 || std::strcmp(c, "2") == 0;
     e->wire_codec_ = v2 ? 2 : 1;
+    e->wire_split_ = v3 ? 1 : std::getenv("TSG_WIRE_PACK") ? 0 : kWireSplitDefault;
     e->wire_mode_ = std::strncmp(c, "force", 5) == 0 && (c[5] == 0 || v2) ? 2 : std::atoi(c) != 0 ? 1 : 0;
   }
   if (const char* c = std::getenv("TSG_WIRE_PACK_THREADS")) e->wire_threads_n_ = std::max(0, std::min(16, std::atoi(c)));
@@ -2999,6 +3006,7 @@ struct WireFeed {
   uint64_t strip = 0;
   bool force = false;                  // the feeder waits for the packers instead of sending raw strips
   bool v2 = false;                     // the 6-bit codec (wirepack.h); else the 7-bit one
+  bool split = false;                  // v2: the packers may write split blocks
   int npackers = 0;
   int ncopy = 1;                       // copy streams the strip copies alternate over
   bool timeline = false;
@@ -3091,7 +3099,7 @@ void WireFeed::pack_loop() {
     Wire2Stats modes;
     if (v2) {
       head += wire2_alpha_bytes(n);
-      pl = wire_pack2(p, n, w.h + head, table, w.h + tab, kWireAuto, &modes);
+      pl = wire_pack2(p, n, w.h + head, table, w.h + tab, kWireAuto, &modes, split);
     } else {
       pl = wire_pack(p, n, w.h + tab, table, kWireAuto);
       for (size_t b = 0; b < wire_blocks(n); ++b) ++(table[b] & kWireRawBit ? modes.blocks_raw : modes.blocks7);
@@ -3224,7 +3232,7 @@ bool WireFeed::feed_segment(size_t si, std::string* err) {
         // (the slot is this thread's until its unpack is reaped)
         const Wire2Stats& m = slots[id].modes;
         modes.blocks6 += m.blocks6; modes.blocks7 += m.blocks7; modes.blocks_raw += m.blocks_raw;
-        modes.escaped += m.escaped;
+        modes.escaped += m.escaped; modes.blocks_split += m.blocks_split;
       }
     }
     ++issued;
@@ -3245,13 +3253,15 @@ bool WireFeed::feed_segment(size_t si, std::string* err) {
     raw += nraw;
     this->modes.blocks6 += modes.blocks6; this->modes.blocks7 += modes.blocks7;
     this->modes.blocks_raw += modes.blocks_raw; this->modes.escaped += modes.escaped;
+    this->modes.blocks_split += modes.blocks_split;
   }
   cv.notify_all();
   if (timeline) std::fprintf(stderr, "[tsg tl] seg %zu wire: %u strips packed, %u raw, %llu bytes sent; blocks 6-bit %llu, "
-                             "7-bit %llu, raw %llu, %llu bytes escaped\n", si, npacked, nraw,
+                             "7-bit %llu, raw %llu, split %llu, %llu bytes escaped\n", si, npacked, nraw,
                              static_cast<unsigned long long>(sent), static_cast<unsigned long long>(modes.blocks6),
                              static_cast<unsigned long long>(modes.blocks7),
                              static_cast<unsigned long long>(modes.blocks_raw),
+                             static_cast<unsigned long long>(modes.blocks_split),
                              static_cast<unsigned long long>(modes.escaped));
   return true;
 }
@@ -3305,6 +3315,9 @@ bool WireFeed::start(Engine& eng, Lane* ln, int device, const std::vector<Segmen
   f->strip = eng.wire_strip_;
   f->force = eng.wire_mode_ == 2;
   f->v2 = eng.wire_codec_ == 2;
+  uint64_t total = 0;
+  for (const Segment& sg : segs) total += sg.bytes;
+  f->split = f->v2 && (eng.wire_split_ > 0 || (eng.wire_split_ < 0 && wire_have_vbmi2() && total >= kWireDenseMinBytes));
   f->npackers = np;
   f->ncopy = eng.wire_copy_streams_;
   f->timeline = eng.host_profile_;
@@ -3348,7 +3361,7 @@ void WireFeed::wind_down(ScanStats* st) {
     eng->wire_busy_ = false;
   }
   if (timeline) std::fprintf(stderr, "[tsg tl] wire: %d packers busy %.3f ms in all (%s codec, path %d)\n", npackers,
-                             pack_ms, v2 ? "6-bit" : "7-bit", v2 ? wire2_path(kWireAuto) : wire_have_avx2() ? 2 : 1);
+                             pack_ms, split ? "6-bit with split blocks" : v2 ? "6-bit" : "7-bit", v2 ? wire2_path(kWireAuto) : wire_have_avx2() ? 2 : 1);
   st->wire_bytes += wire_bytes;
   st->packed_strips += packed;
   st->raw_strips += raw;
@@ -3357,6 +3370,7 @@ void WireFeed::wind_down(ScanStats* st) {
   st->blocks_7bit += modes.blocks7;
   st->blocks_raw += modes.blocks_raw;
   st->escaped_bytes += modes.escaped;
+  st->blocks_split += modes.blocks_split;
 }
 
 void Engine::wire_packer_main() {

@@ -1,10 +1,12 @@
 // Host side of the wire packing (wirepack.h).  The 7-bit codec: a scalar 64-bit
 // SWAR path and an AVX2 path, chosen at run time, and the reference unpack.  The
-// 6-bit codec with escapes: scalar, AVX2 and AVX-512 VBMI paths and its unpack.
+// 6-bit codec with escapes: scalar, AVX2 and AVX-512 VBMI paths and its unpack;
+// its split blocks: scalar, AVX2 (lookup only) and AVX-512 VBMI2 paths.
 #include "wirepack.h"
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
 
 #if defined(__x86_64__)
 #include <immintrin.h>
@@ -279,6 +281,195 @@ __attribute__((target("avx512f,avx512bw,avx512vl,avx512vbmi"))) uint32_t pack6_v
   *acc |= high ? 0x80u : 0u;
   return pack6_groups_scalar(src, len, nv * 16, a, dst, esc, nesc, limit, acc);
 }
+
+// pack6_vbmi with the escaped bytes of a vector gathered by one register-form
+// byte compress (the store runs up to 63 bytes past them, inside esc)
+__attribute__((target("avx512f,avx512bw,avx512vl,avx512vbmi,avx512vbmi2"))) uint32_t pack6_vbmi2(
+    const uint8_t* src, size_t len, const Alphabet& a, uint8_t* dst, uint8_t* esc, uint32_t limit, uint32_t* acc) {
+  const __m512i t0 = _mm512_load_si512(a.inv), t1 = _mm512_load_si512(a.inv + 64);
+  const __m512i k63 = _mm512_set1_epi8(63);
+  const __m512i mul1 = _mm512_set1_epi16(0x4001), mul2 = _mm512_set1_epi32(0x10000001);
+  alignas(64) uint8_t idx[64];
+  for (int j = 0; j < 64; ++j) idx[j] = static_cast<uint8_t>(j < 48 ? j / 3 * 4 + j % 3 : 0);
+  const __m512i gather = _mm512_load_si512(idx);
+  __mmask64 high = 0;
+  uint32_t nesc = 0;
+  const size_t nv = len / 64;
+  for (size_t i = 0; i < nv; ++i) {
+    const __m512i x = _mm512_loadu_si512(src + 64 * i);
+    const __mmask64 hi = _mm512_movepi8_mask(x);
+    high |= hi;
+    const __m512i r = _mm512_permutex2var_epi8(t0, x, t1);
+    const __m512i c = _mm512_mask_mov_epi8(_mm512_sub_epi8(k63, r), hi, k63);
+    const __mmask64 m = _mm512_cmpeq_epi8_mask(c, k63);
+    __m512i p = _mm512_madd_epi16(_mm512_maddubs_epi16(c, mul1), mul2);
+    p = _mm512_permutexvar_epi8(gather, p);
+    _mm512_storeu_si512(dst + 48 * i, p);
+    if (m) {
+      _mm512_storeu_si512(esc + nesc, _mm512_maskz_compress_epi8(m, x));
+      nesc += static_cast<uint32_t>(__builtin_popcountll(m));
+      if (nesc >= limit) return kAbort;
+    }
+  }
+  *acc |= high ? 0x80u : 0u;
+  return pack6_groups_scalar(src, len, nv * 16, a, dst, esc, nesc, limit, acc);
+}
+#endif
+
+// ---- split blocks (wirepack.h).  A block is first taken apart into one value
+// per byte of each stream (scan), which also gives every mode's size; the
+// streams are packed into the destination (emit) only once split is chosen.
+
+struct Split {
+  alignas(64) uint8_t mask[kWireBlock / 8 + 64];
+  alignas(64) uint8_t nib[kWireBlock + 128];     // the hot codes
+  alignas(64) uint8_t five[kWireBlock + 128];    // the 5-bit values
+  alignas(64) uint8_t esc[kWireBlock + 128];     // the escaping bytes
+  uint32_t h = 0, e = 0;
+  uint32_t e6 = 0;                               // bytes the 6-bit mode would escape
+  bool high = false;                             // a byte >= 0x80 was seen
+};
+
+// (the vector emit reads whole vectors of values: zeros follow the last one)
+inline void split_finish(Split* s, size_t len, uint32_t h, uint32_t e, uint32_t e6, bool high) {
+  std::memset(s->nib + h, 0, 64);
+  std::memset(s->five + (len - h), 0, 64);
+  s->h = h; s->e = e; s->e6 = e6; s->high = high;
+}
+
+// bytes [i0, len) of a block whose 6-bit codes are in code[]
+inline void split_scan_codes(const uint8_t* src, const uint8_t* code, size_t i0, size_t len, Split* s, uint32_t h,
+                             uint32_t e, uint32_t e6, uint32_t acc) {
+  uint32_t w = static_cast<uint32_t>(i0) - h;
+  for (size_t i = i0; i < len; ++i) {
+    const uint8_t x = src[i], c = code[i];
+    acc |= x;
+    if (i % 8 == 0) s->mask[i / 8] = 0;
+    if (c < kWire2Hot) {
+      s->mask[i / 8] |= static_cast<uint8_t>(1u << (i % 8));
+      s->nib[h++] = c;
+    } else if (c < kWire2Warm) {
+      s->five[w++] = static_cast<uint8_t>(c - kWire2Hot);
+    } else {
+      s->five[w++] = kWire2Escape5;
+      s->esc[e++] = x;
+      e6 += c == kWire2Escape;
+    }
+  }
+  split_finish(s, len, h, e, e6, (acc & 0x80) != 0);
+}
+
+void split_scan_scalar(const uint8_t* src, size_t len, const Alphabet& a, Split* s) {
+  uint8_t code[kWireBlock];
+  for (size_t i = 0; i < len; ++i) code[i] = a.code[src[i]];
+  split_scan_codes(src, code, 0, len, s, 0, 0, 0, 0);
+}
+
+void split_emit_scalar(const Split& s, size_t len, uint8_t* d) {
+  const size_t M = (len + 7) / 8, N = (s.h + 1) / 2, nf = len - s.h, F = (5 * nf + 7) / 8;
+  std::memcpy(d, s.mask, M);
+  d += M;
+  for (size_t j = 0; j < N; ++j) d[j] = static_cast<uint8_t>(s.nib[2 * j] | s.nib[2 * j + 1] << 4);
+  d += N;
+  for (size_t g = 0; 5 * g < F; ++g) {
+    uint64_t v = 0;
+    for (int j = 0; j < 8; ++j) v |= static_cast<uint64_t>(s.five[8 * g + j]) << (5 * j);
+    for (size_t j = 0; j < 5 && 5 * g + j < F; ++j) d[5 * g + j] = static_cast<uint8_t>(v >> (8 * j));
+  }
+  d += F;
+  std::memcpy(d, s.esc, s.e);
+  std::memset(d + s.e, 0, wire2_split_bytes(len, s.h, s.e) - (M + N + F + s.e));
+}
+
+#if defined(__x86_64__)
+// the codes by the lookup of pack6_avx2, the streams by the scalar loop
+__attribute__((target("avx2"))) void split_scan_avx2(const uint8_t* src, size_t len, const Alphabet& a, Split* s) {
+  __m256i T[8], X[8];
+  for (int k = 0; k < 8; ++k) {
+    T[k] = _mm256_broadcastsi128_si256(_mm_load_si128(reinterpret_cast<const __m128i*>(a.inv + 16 * k)));
+    X[k] = _mm256_set1_epi8(static_cast<char>(16 * k));
+  }
+  const __m256i k70 = _mm256_set1_epi8(0x70), k63 = _mm256_set1_epi8(63);
+  alignas(32) uint8_t code[kWireBlock];
+  const size_t nv = len / 32;
+  for (size_t i = 0; i < nv; ++i) {
+    const __m256i x = _mm256_loadu_si256(reinterpret_cast<const __m256i*>(src + 32 * i));
+    __m256i r = _mm256_shuffle_epi8(T[0], _mm256_adds_epu8(x, k70));
+    for (int k = 1; k < 8; ++k)
+      r = _mm256_or_si256(r, _mm256_shuffle_epi8(T[k], _mm256_adds_epu8(_mm256_xor_si256(x, X[k]), k70)));
+    _mm256_store_si256(reinterpret_cast<__m256i*>(code + 32 * i), _mm256_sub_epi8(k63, r));
+  }
+  for (size_t i = 32 * nv; i < len; ++i) code[i] = a.code[src[i]];
+  split_scan_codes(src, code, 0, len, s, 0, 0, 0, 0);
+}
+
+// Per 64 bytes: the lookup of pack6_vbmi, the hot mask, and one register-form
+// byte compress per stream, each stored whole at the stream's end (so up to
+// 63 bytes past it, inside the scratch).  A short last vector is loaded under
+// a mask.
+__attribute__((target("avx512f,avx512bw,avx512vl,avx512vbmi,avx512vbmi2"))) void split_scan_vbmi2(
+    const uint8_t* src, size_t len, const Alphabet& a, Split* s) {
+  const __m512i t0 = _mm512_load_si512(a.inv), t1 = _mm512_load_si512(a.inv + 64);
+  const __m512i k63 = _mm512_set1_epi8(63), khot = _mm512_set1_epi8(static_cast<char>(kWire2Hot));
+  const __m512i kwarm = _mm512_set1_epi8(static_cast<char>(kWire2Warm)), k31 = _mm512_set1_epi8(kWire2Escape5);
+  uint32_t h = 0, w = 0, e = 0, e6 = 0;
+  __mmask64 high = 0;
+  for (size_t i = 0; i < len; i += 64) {
+    const __mmask64 valid = len - i >= 64 ? ~0ull : (1ull << (len - i)) - 1;
+    const __m512i x = _mm512_maskz_loadu_epi8(valid, src + i);
+    const __mmask64 hi = _mm512_movepi8_mask(x);
+    high |= hi;
+    const __m512i r = _mm512_permutex2var_epi8(t0, x, t1);
+    const __m512i c = _mm512_mask_mov_epi8(_mm512_sub_epi8(k63, r), hi, k63);
+    const __mmask64 hot = _mm512_cmplt_epu8_mask(c, khot) & valid, rest = ~hot & valid;
+    const uint64_t hot_bits = hot;
+    std::memcpy(s->mask + i / 8, &hot_bits, 8);
+    _mm512_storeu_si512(s->nib + h, _mm512_maskz_compress_epi8(hot, c));
+    h += static_cast<uint32_t>(__builtin_popcountll(hot));
+    const __m512i f = _mm512_min_epu8(_mm512_sub_epi8(c, khot), k31);
+    _mm512_storeu_si512(s->five + w, _mm512_maskz_compress_epi8(rest, f));
+    w += static_cast<uint32_t>(__builtin_popcountll(rest));
+    const __mmask64 out = _mm512_cmpge_epu8_mask(c, kwarm) & valid;
+    if (out) {
+      _mm512_storeu_si512(s->esc + e, _mm512_maskz_compress_epi8(out, x));
+      e += static_cast<uint32_t>(__builtin_popcountll(out));
+      e6 += static_cast<uint32_t>(__builtin_popcountll(_mm512_cmpeq_epi8_mask(c, k63) & valid));
+    }
+  }
+  split_finish(s, len, h, e, e6, high != 0);
+}
+
+// The fixed 2 -> 1 and 8 -> 5 packs of the two runs of values, whole vectors at
+// a time: every store runs past its stream (by at most 63 bytes) into what is
+// written after it, the last one past the block into the next block's bytes or
+// the destination's slack.
+__attribute__((target("avx512f,avx512bw,avx512vl,avx512vbmi"))) void split_emit_vbmi(const Split& s, size_t len,
+                                                                                     uint8_t* d) {
+  const size_t M = (len + 7) / 8, N = (s.h + 1) / 2, nf = len - s.h, F = (5 * nf + 7) / 8;
+  std::memcpy(d, s.mask, M);
+  d += M;
+  const __m512i two = _mm512_set1_epi16(0x1001);
+  for (size_t j = 0; j < s.h; j += 64) {
+    const __m512i v = _mm512_load_si512(s.nib + j);
+    _mm256_storeu_si256(reinterpret_cast<__m256i*>(d + j / 2), _mm512_cvtepi16_epi8(_mm512_maddubs_epi16(v, two)));
+  }
+  d += N;
+  alignas(64) uint8_t idx[64];
+  for (int j = 0; j < 64; ++j) idx[j] = static_cast<uint8_t>(j < 40 ? j / 5 * 8 + j % 5 : 5);   // (byte 5 is zero)
+  const __m512i gather = _mm512_load_si512(idx);
+  const __m512i mul1 = _mm512_set1_epi16(0x2001), mul2 = _mm512_set1_epi32(0x04000001);
+  const __m512i lo20 = _mm512_set1_epi64(0xFFFFF), hi20 = _mm512_set1_epi64(0xFFFFF00000ll);
+  for (size_t j = 0; j < nf; j += 64) {
+    const __m512i v = _mm512_load_si512(s.five + j);
+    // 8 values -> four 10-bit words -> two 20-bit dwords -> 40 bits of a qword
+    const __m512i q = _mm512_madd_epi16(_mm512_maddubs_epi16(v, mul1), mul2);
+    const __m512i p = _mm512_or_si512(_mm512_and_si512(q, lo20), _mm512_and_si512(_mm512_srli_epi64(q, 12), hi20));
+    _mm512_storeu_si512(d + j / 8 * 5, _mm512_permutexvar_epi8(gather, p));
+  }
+  d += F;
+  std::memcpy(d, s.esc, s.e);
+  std::memset(d + s.e, 0, wire2_split_bytes(len, s.h, s.e) - (M + N + F + s.e));
+}
 #endif
 
 }  // namespace
@@ -293,6 +484,15 @@ bool wire_have_vbmi() {
 #endif
 }
 
+bool wire_have_vbmi2() {
+#if defined(__x86_64__)
+  static const bool have = wire_have_vbmi() && __builtin_cpu_supports("avx512vbmi2");
+  return have;
+#else
+  return false;
+#endif
+}
+
 int wire2_path(int path) {
   if (path == kWireScalar) return kWireScalar;
   if (path != kWireAvx2 && wire_have_vbmi()) return kWireVbmi;
@@ -300,19 +500,25 @@ int wire2_path(int path) {
 }
 
 size_t wire_pack2(const uint8_t* src, size_t n, uint8_t* dst, uint32_t* table, uint8_t* alpha, int path,
-                  Wire2Stats* stats) {
+                  Wire2Stats* stats, bool split) {
   uint32_t (*pack6)(const uint8_t*, size_t, const Alphabet&, uint8_t*, uint8_t*, uint32_t, uint32_t*) = pack6_scalar;
   uint64_t (*pack7)(const uint8_t*, size_t, uint8_t*) = pack_block_scalar;
+  void (*split_scan)(const uint8_t*, size_t, const Alphabet&, Split*) = split_scan_scalar;
+  void (*split_emit)(const Split&, size_t, uint8_t*) = split_emit_scalar;
 #if defined(__x86_64__)
   const int used = wire2_path(path);
   if (used != kWireScalar) pack7 = pack_block_avx2;
   if (used == kWireAvx2) pack6 = pack6_avx2;
-  if (used == kWireVbmi) pack6 = pack6_vbmi;
+  if (used == kWireVbmi) pack6 = wire_have_vbmi2() ? pack6_vbmi2 : pack6_vbmi;
+  if (used != kWireScalar) { split_scan = split_scan_avx2; }
+  if (used == kWireVbmi) split_emit = split_emit_vbmi;
+  if (used == kWireVbmi && wire_have_vbmi2()) split_scan = split_scan_vbmi2;
 #endif
   if (n) std::memset(alpha, 0, wire2_alpha_bytes(n));
   Wire2Stats st;
   Alphabet a;
   uint8_t esc[kWireBlock + 64];
+  std::unique_ptr<Split> sp(split ? new Split : nullptr);
   size_t o = 0;
   const size_t nb = wire_blocks(n);
   for (size_t b = 0; b < nb; ++b) {
@@ -325,7 +531,23 @@ size_t wire_pack2(const uint8_t* src, size_t n, uint8_t* dst, uint32_t* table, u
     // 6-bit is chosen only below the raw size: once cb + escapes reach len it is out
     const uint32_t limit = len > cb ? static_cast<uint32_t>(len - cb) : 0;
     uint32_t acc = 0;
-    const uint32_t nesc = limit ? pack6(s, len, a, dst + o, esc, limit, &acc) : kAbort;
+    bool no6 = false;
+    if (split) {
+      // every mode's size from one scan; 6-bit and 7-bit blocks are then packed as without split
+      split_scan(s, len, a, sp.get());
+      const size_t size7 = sp->high ? len : wire_packed_len(len), size6 = cb + ((sp->e6 + 15) & ~size_t(15));
+      const size_t sizes = wire2_split_bytes(len, sp->h, sp->e);
+      if (sizes < len && sizes < size7 && sizes < size6) {
+        split_emit(*sp, len, dst + o);
+        table[b] = static_cast<uint32_t>(o) | kWireRawBit | kWire6Bit;
+        o += sizes;
+        ++st.blocks_split;
+        st.escaped += sp->e;
+        continue;
+      }
+      no6 = !(size6 < len && size6 < size7);
+    }
+    const uint32_t nesc = limit && !no6 ? pack6(s, len, a, dst + o, esc, limit, &acc) : kAbort;
     if (nesc != kAbort) {
       const size_t size6 = cb + ((nesc + 15) & ~size_t(15));
       const bool ascii = !(acc & 0x80);
@@ -364,7 +586,26 @@ void wire_unpack2(const uint8_t* packed, const uint32_t* table, const uint8_t* a
     const size_t len = n - at < kWireBlock ? n - at : kWireBlock;
     const uint8_t* s = packed + (table[b] & ~(kWireRawBit | kWire6Bit));
     uint8_t* d = dst + at;
-    if (table[b] & kWireRawBit) {
+    if ((table[b] & kWireRawBit) && (table[b] & kWire6Bit)) {
+      const uint8_t* al = alpha + at / kWire2Region * kWire2Alpha;
+      size_t h = 0;
+      for (size_t i = 0; i < len; ++i) h += s[i / 8] >> (i % 8) & 1;
+      const uint8_t* nib = s + (len + 7) / 8;
+      const uint8_t* five = nib + (h + 1) / 2;
+      const uint8_t* e = five + (5 * (len - h) + 7) / 8;
+      size_t jn = 0, jf = 0;
+      for (size_t i = 0; i < len; ++i) {
+        if (s[i / 8] >> (i % 8) & 1) {
+          d[i] = al[nib[jn / 2] >> (4 * (jn % 2)) & 15];
+          ++jn;
+        } else {
+          const size_t bit = 5 * jf++;
+          const uint32_t lo = five[bit >> 3], hi = (bit & 7) > 3 ? five[(bit >> 3) + 1] : 0;
+          const uint32_t c = ((lo | hi << 8) >> (bit & 7)) & 31;
+          d[i] = c == kWire2Escape5 ? *e++ : al[kWire2Hot + c];
+        }
+      }
+    } else if (table[b] & kWireRawBit) {
       std::memcpy(d, s, len);
     } else if (table[b] & kWire6Bit) {
       const uint8_t* al = alpha + at / kWire2Region * kWire2Alpha;

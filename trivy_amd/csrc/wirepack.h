@@ -29,8 +29,8 @@
 // head: wire2_alpha_bytes(n) bytes, which travel between the table and the
 // packed bytes.
 //
-// A block of len bytes is written in the smallest of three modes; of two equal
-// sizes raw is preferred to 7-bit and 7-bit to 6-bit:
+// A block of len bytes is written in the smallest of its modes (three, or four
+// where split blocks are allowed; the tie order follows the list):
 //
 //   * raw (kWireRawBit): len bytes unchanged;
 //   * 7-bit (no mode bit): as above, (len + 7) / 8 * 7 bytes; only for a block
@@ -45,8 +45,31 @@
 //     is pad16((len + 3) / 4 * 3) + pad16(e): a full block goes 6-bit instead of
 //     7-bit up to e = 496 and instead of raw up to e = 1008.
 //
-// table[b] = offset | mode bits.  Every block but a strip's last has a size
-// that is a multiple of 16, so offsets are, and they stay below 2^30.
+//   * split (kWireRawBit and kWire6Bit both set; only where the packer is
+//     allowed to, see wire_pack2): the codes are those of the 6-bit mode, that
+//     is positions in the region's alphabet.  A byte is "hot" when its code is
+//     below 16, "warm" when it is 16..46; every other byte (code 47..62, or
+//     not in the alphabet) escapes.  With h hot bytes and e escaping ones the
+//     block is four streams laid back to back at byte granularity, every pad
+//     bit zero, the total padded with zero bytes to a multiple of 16:
+//       - the mask, (len + 7) / 8 bytes: bit k % 8 of byte k / 8 is set when
+//         byte k of the block is hot;
+//       - the hot codes in block order, 4 bits each, the j-th in bits 4j ..
+//         4j+3 of a little-endian bit string of (h + 1) / 2 bytes;
+//       - one 5-bit value for every other byte in block order, the j-th in
+//         bits 5j .. 5j+4 of a little-endian bit string of
+//         (5 (len - h) + 7) / 8 bytes: code - 16 for a warm byte, 31 for one
+//         that escapes;
+//       - the e escaping bytes in block order.
+//     The size is wire2_split_bytes(len, h, e) =
+//       pad16((len + 7) / 8 + (h + 1) / 2 + (5 (len - h) + 7) / 8 + e),
+//     for a full block pad16(3072 - h / 8 + e) where h is a multiple of 8.
+//
+// Of equal sizes raw is preferred to 7-bit, 7-bit to 6-bit and 6-bit to split.
+//
+// table[b] = offset | mode bits.  Every block has a size that is a multiple of
+// 16 except a strip's last (raw or 7-bit), so offsets are multiples of 16, and
+// they stay below 2^30.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -91,23 +114,36 @@ constexpr uint32_t kWire2Escape = 63;
 
 struct Wire2Stats {
   uint64_t blocks6 = 0, blocks7 = 0, blocks_raw = 0;
-  uint64_t escaped = 0;                          // escaped bytes of the 6-bit blocks
+  uint64_t escaped = 0;                          // escaped bytes of the 6-bit and split blocks
+  uint64_t blocks_split = 0;
 };
 
 inline size_t wire2_regions(size_t n) { return (n + kWire2Region - 1) / kWire2Region; }
 inline size_t wire2_alpha_bytes(size_t n) { return (wire2_regions(n) * kWire2Alpha + 255) & ~size_t(255); }
 inline size_t wire2_code_bytes(size_t block_bytes) { return ((block_bytes + 3) / 4 * 3 + 15) & ~size_t(15); }
 inline size_t wire2_bound(size_t n) { return n + 16 + kWireSlack; }
+constexpr uint32_t kWire2Hot = 16;               // split mode: codes below it go in 4 bits
+constexpr uint32_t kWire2Warm = 47;              // codes kWire2Hot .. kWire2Warm - 1 go in 5 bits; the rest escape
+constexpr uint32_t kWire2Escape5 = 31;
+// a split block of len bytes, h of them hot and e escaping
+inline size_t wire2_split_bytes(size_t len, size_t h, size_t e) {
+  return ((len + 7) / 8 + (h + 1) / 2 + (5 * (len - h) + 7) / 8 + e + 15) & ~size_t(15);
+}
 
 bool wire_have_vbmi();
+// AVX-512 VBMI2 (byte compress) besides what wire_have_vbmi() asks for: the
+// kWireVbmi path then packs split blocks, and the escaped bytes of 6-bit ones,
+// with it; without it split blocks are packed by the AVX2 path.
+bool wire_have_vbmi2();
 // The path wire_pack2 runs for a requested one: the request itself where the
 // CPU has it, else the best below it (kWireAuto: the CPU's best).
 int wire2_path(int path);
 // Packs src[0, n) into dst (wire2_bound(n) bytes), table (wire_blocks(n)
 // entries) and alpha (wire2_alpha_bytes(n) bytes, written whole); returns the
-// packed length.  Every path gives the same bytes.
+// packed length.  Every path gives the same bytes.  Split blocks are written
+// only with `split` set; without it the bytes are those of the three modes.
 size_t wire_pack2(const uint8_t* src, size_t n, uint8_t* dst, uint32_t* table, uint8_t* alpha, int path,
-                  Wire2Stats* stats);
+                  Wire2Stats* stats, bool split = false);
 // The reference unpack; reads nothing past the packed bytes.
 void wire_unpack2(const uint8_t* packed, const uint32_t* table, const uint8_t* alpha, size_t n, uint8_t* dst);
 // As wire_unpack_device_probe, with the v2 kernel.

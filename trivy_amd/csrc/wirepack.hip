@@ -63,6 +63,103 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t lane) {
   return v;
 }
 
+// A split block (wirepack.h) of len bytes at src, by the whole workgroup; lane
+// t owns output bytes 16t .. 16t+15.
+//   1. The lane reads its 16 mask bits from global memory; an exclusive scan
+//      of their popcounts over the workgroup (a wave scan and the four wave
+//      totals in LDS) gives its first hot code and, as 16t less that, its
+//      first 5-bit value; the total gives the block's hot count, hence the
+//      size of the three streams in front of the escaped bytes.
+//   2. Exactly those streams (rounded up to 16 bytes, which the block's own
+//      padding covers) and the region's alphabet go to LDS.
+//   3. The lane takes the three dwords that hold its hot codes and the four
+//      that hold its 5-bit values (reads of LDS may run past the streams, never
+//      past sh; what they bring is not used), counts the escapes among its
+//      values, and a second scan gives its first escaped byte, read from
+//      global memory.
+//   4. One 16-byte store; single bytes only in a strip's short last block.
+__device__ __forceinline__ void unpack_split_block(const uint8_t* __restrict__ src, const uint8_t* __restrict__ alpha,
+                                                   uint32_t len, uint8_t* __restrict__ out, uint4* sh, uint4* sh_alpha,
+                                                   uint32_t* sh_wave, uint32_t* sh_wave2) {
+  const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+  const uint32_t mine = 16 * t < len ? min(16u, len - 16 * t) : 0u;   // output bytes of this lane
+  const uint32_t mb = (len + 7) / 8;
+  uint32_t m = 0;
+  if (mine > 8) m = reinterpret_cast<const uint16_t*>(src)[t];
+  else if (mine) m = src[2 * t];
+  const uint32_t hot = __popc(m), warm = mine - hot;                   // (mask bits past len are zero)
+  const uint32_t incl = wave_incl_scan(hot, lane);
+  if (lane == 63) sh_wave[wave] = incl;
+  if (t < kWire2Alpha / 16) sh_alpha[t] = reinterpret_cast<const uint4*>(alpha)[t];
+  __syncthreads();
+  uint32_t ni = incl - hot, h = 0;
+  for (uint32_t v = 0; v < 4; ++v) {
+    const uint32_t x = sh_wave[v];
+    ni += v < wave ? x : 0u;
+    h += x;
+  }
+  h = min(h, len);                                                     // (no more than a well-formed mask has)
+  const uint32_t fb = mb + (h + 1) / 2;                                // the 5-bit values' first byte
+  const uint32_t sbytes = fb + (5 * (len - h) + 7) / 8;                // <= 3073 < sizeof sh
+  if (16 * t < sbytes) sh[t] = reinterpret_cast<const uint4*>(src)[t];
+  __syncthreads();
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(sh);
+  unsigned long long nibs = 0, f0 = 0, f1 = 0;
+  uint32_t nesc = 0;
+  if (mine) {
+    {
+      const uint32_t at = mb + (ni >> 1), d = at >> 2, sft = (at & 3u) * 8 + (ni & 1u) * 4;
+      const unsigned long long lo = w[d] | (static_cast<unsigned long long>(w[d + 1]) << 32);
+      nibs = sft ? (lo >> sft) | (static_cast<unsigned long long>(w[d + 2]) << (64 - sft)) : lo;
+    }
+    {
+      const uint32_t bit = 8 * fb + 5 * (16 * t - ni), d = bit >> 5, sft = bit & 31u;
+      const unsigned long long lo = w[d] | (static_cast<unsigned long long>(w[d + 1]) << 32);
+      const unsigned long long hi = w[d + 2] | (static_cast<unsigned long long>(w[d + 3]) << 32);
+      f0 = sft ? (lo >> sft) | (hi << (64 - sft)) : lo;
+      f1 = hi >> sft;
+    }
+    unsigned long long g0 = f0, g1 = f1;
+#pragma unroll
+    for (uint32_t j = 0; j < 16; ++j) {
+      nesc += (j < warm && (g0 & 31u) == kWire2Escape5) ? 1u : 0u;
+      g0 = (g0 >> 5) | (g1 << 59);
+      g1 >>= 5;
+    }
+  }
+  const uint32_t incl2 = wave_incl_scan(nesc, lane);
+  if (lane == 63) sh_wave2[wave] = incl2;
+  __syncthreads();
+  uint32_t e = incl2 - nesc;                                           // index of the lane's first escaped byte
+  for (uint32_t v = 0; v < wave; ++v) e += sh_wave2[v];
+  if (mine) {
+    const uint8_t* __restrict__ esc = src + sbytes;
+    const uint8_t* al = reinterpret_cast<const uint8_t*>(sh_alpha);
+    uint32_t o[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (uint32_t k = 0; k < 16; ++k) {
+      uint32_t v;
+      if ((m >> k) & 1u) {
+        v = al[nibs & 15u];
+        nibs >>= 4;
+      } else {
+        const uint32_t c = static_cast<uint32_t>(f0) & 31u;
+        f0 = (f0 >> 5) | (f1 << 59);
+        f1 >>= 5;
+        v = al[kWire2Hot + c];
+        if (c == kWire2Escape5) v = k < mine ? esc[e++] : 0u;
+      }
+      o[k >> 2] |= v << (8 * (k & 3));
+    }
+    if (mine == 16) {
+      reinterpret_cast<uint4*>(out)[t] = make_uint4(o[0], o[1], o[2], o[3]);
+    } else {
+      for (uint32_t k = 0; k < mine; ++k) out[16 * t + k] = static_cast<uint8_t>(o[k >> 2] >> (8 * (k & 3)));
+    }
+  }
+  __syncthreads();                       // sh, sh_alpha and the wave totals are rewritten by the next block
+}
+
 }  // namespace
 
 // One workgroup of 256 lanes per block of kWireBlock bytes (grid-stride over
@@ -98,7 +195,8 @@ __global__ __launch_bounds__(256) void tsg_wire_unpack(const uint8_t* __restrict
   }
 }
 
-// The v2 unpack (wirepack.h): the same grid and blocks, three modes.  land =
+// The v2 unpack (wirepack.h): the same grid and blocks, four modes (a split
+// block goes through unpack_split_block above).  land =
 // the block table (tab_bytes), the alphabets (alpha_bytes, 64 bytes per region
 // of 16 blocks) and the packed bytes.  Raw and 7-bit blocks go as in
 // tsg_wire_unpack.  A 6-bit block's codes (at most 3072 bytes, a multiple of
@@ -108,12 +206,15 @@ __global__ __launch_bounds__(256) void tsg_wire_unpack(const uint8_t* __restrict
 // (a wave scan and the four wave totals in LDS) gives its first escaped byte,
 // and it reads those from the block's tail in global memory.  Loads of a 6-bit
 // block stay inside its payload; a short 7-bit block's may run up to 15 bytes
-// past it (kWireSlack).  Nothing is stored at or past dst + n.
+// past it (kWireSlack).  A split block's loads stay inside its payload too:
+// the mask bits a lane owns, the three streams rounded up to 16 bytes (which
+// the block's own pad to 16 covers) and its escaped bytes one by one.  Nothing
+// is stored at or past dst + n.
 __global__ __launch_bounds__(256) void tsg_wire_unpack2(const uint8_t* __restrict__ land, uint32_t tab_bytes,
                                                          uint32_t alpha_bytes, uint8_t* __restrict__ dst, uint32_t n) {
   __shared__ uint4 sh[kWireBlockPacked / 16];
   __shared__ uint4 sh_alpha[kWire2Alpha / 16];
-  __shared__ uint32_t sh_wave[4];
+  __shared__ uint32_t sh_wave[4], sh_wave2[4];
   const uint32_t* __restrict__ tab = reinterpret_cast<const uint32_t*>(land);
   const uint8_t* __restrict__ alphas = land + tab_bytes;
   const uint8_t* __restrict__ data = alphas + alpha_bytes;
@@ -124,7 +225,12 @@ __global__ __launch_bounds__(256) void tsg_wire_unpack2(const uint8_t* __restric
     const uint32_t len = min(kWireBlock, n - b * kWireBlock);
     const uint8_t* __restrict__ src = data + (ent & ~(kWireRawBit | kWire6Bit));
     uint8_t* __restrict__ out = dst + static_cast<size_t>(b) * kWireBlock;
-    if (ent & kWireRawBit) {             // (the mode is uniform over the workgroup)
+    if ((ent & kWireRawBit) && (ent & kWire6Bit)) {   // (the mode is uniform over the workgroup)
+      unpack_split_block(src, alphas + static_cast<size_t>(b / (kWire2Region / kWireBlock)) * kWire2Alpha, len, out, sh,
+                         sh_alpha, sh_wave, sh_wave2);
+      continue;
+    }
+    if (ent & kWireRawBit) {
       copy_raw_lane(src, t, len, out);
       continue;
     }
