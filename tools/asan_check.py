@@ -13,8 +13,9 @@ configs, protobuf messages, an fs tree) with fixtures and truncated /
 mutated copies; a fourth (--concurrency) runs the concurrent host code: the
 per-file queue with 16 callers and with an injected failure, the streamed
 layer / tree pipelines, the result reaper and threaded SecretVec construction;
-a fifth (device) runs the CPU model of the device-only scan over the first
-corpus with the batch freed before the confirmation.
+a fifth (device) runs the CPU model of the device-only scan over both
+corpora with the batch freed before the confirmation.  Only build.HOST_SRCS
+are instrumented: host code inside the .hip files is not (the log says which).
 
   python tools/asan_check.py [--mb 8] [--out profiles/r3n_asan.log]
 """
@@ -180,7 +181,7 @@ def main():
     ap.add_argument("--workdir", default="", help="keep the driver and inputs here")
     ap.add_argument("--cases", default="c2,c5,parsers,concurrency,device",
                     help="comma-separated runs: c2, c5, parsers, concurrency, device (the device-only scan's CPU model "
-                         "over the c2 corpus, its batch freed before the confirmation)")
+                         "over the c2 and c5 corpora, its batch freed before the confirmation)")
     a = ap.parse_args()
     lines = []
     with (tempfile.TemporaryDirectory() if not a.workdir else _Keep(a.workdir)) as td:
@@ -198,19 +199,22 @@ def main():
                    TSAN_OPTIONS="halt_on_error=1:second_deadlock_stack=1")
         write_parsers_case(os.path.join(td, "parsers"))
         rc_all = 0
+        runs = []
         for case in [c for c in a.cases.split(",") if c]:
-            if case == "device":
-                argv = [exe, "--device-model", os.path.join(td, "c2")]
+            if case == "device":             # config 5 adds mode-1 rules and exclude-block pseudo-rules to the confirmation
+                runs += [("device(%s)" % c, [exe, "--device-model", os.path.join(td, c)]) for c in ("c2", "c5")]
             elif case == "parsers":
-                argv = [exe, "--parsers", os.path.join(td, case)]
+                runs.append((case, [exe, "--parsers", os.path.join(td, case)]))
             elif case == "concurrency":      # queue, stream pipelines, reaper, threaded SecretVec
-                argv = [exe, "--concurrency", os.path.join(td, "c2"), os.path.join(td, "parsers")]
+                runs.append((case, [exe, "--concurrency", os.path.join(td, "c2"), os.path.join(td, "parsers")]))
             else:
-                argv = [exe, os.path.join(td, case)]
+                runs.append((case, [exe, os.path.join(td, case)]))
+        for name, argv in runs:
             p = subprocess.run(argv, capture_output=True, text=True, env=env)
-            lines.append("%s rc=%d %s%s" % (case, p.returncode, p.stdout, p.stderr[-4000:]))
+            lines.append("%s rc=%d %s%s" % (name, p.returncode, p.stdout, p.stderr[-4000:]))
             rc_all |= p.returncode
-    text = "sanitizers: %s\n%s" % (" ".join(san), "".join(lines))
+    text = ("sanitizers: %s\ncompiled with them (build.HOST_SRCS): %s\nlinked without them (build.HIP_SRCS, host code "
+            "included): %s\n%s" % (" ".join(san), " ".join(B.HOST_SRCS), " ".join(B.HIP_SRCS), "".join(lines)))
     print(text)
     if a.out:
         with open(a.out, "w") as f:

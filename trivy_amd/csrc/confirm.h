@@ -1,0 +1,60 @@
+// What the host confirmation (confirm.cpp) takes from a segment's GPU passes,
+// in plain host types: no HIP here, so the confirmation builds with the host
+// compiler alone and runs under the host sanitizers (tools/asan_check.py).
+#pragma once
+#include <chrono>
+#include <cstdint>
+#include <memory>
+#include <vector>
+
+#include "threadpool.h"
+
+namespace tsg {
+
+// A candidate as the host sees it (the device's record of the same layout
+// becomes one in GpuOut::finish_copy, engine.hip, and nowhere else).
+struct Cand { uint32_t file, rule; uint64_t start; };
+
+// GPU results of one segment as the host confirmer reads them (the engine's
+// GpuOut adds what belongs to the lane and the device).
+struct SegmentOut {
+  std::vector<Cand> cands;      // (file, rule, start) candidates, unsorted
+  std::vector<uint16_t> nl;     // '\n' count per K1 chunk
+  std::vector<uint32_t> ff;     // per-file flags (fold-special content)
+  uint32_t chunk = 0;           // K1 chunk bytes of this segment (nl[] granularity)
+  // device-only scans: where each file's bytes are in the gather buffer, and
+  // what the gather took.  gbase: the buffer's host address (the CPU model
+  // sets one of its own).
+  const uint8_t* gbase = nullptr;
+  bool gathered = false;
+  uint64_t gather_total = 0, gather_files = 0;
+  std::vector<uint64_t> goff;
+  // the confirmation's plan (plan_confirm): candidates grouped per file, the
+  // files to confirm (largest first) and the rest.  (Built on the driver
+  // thread it delayed the next piece's launch by as much as it saved the
+  // confirming thread: profiles/rd4q_bench_c3prof.log; it is now built while
+  // the next piece's passes run.)
+  bool planned = false;
+  std::vector<uint32_t> per_file, work, light;
+  std::vector<Cand> sorted;
+};
+
+// One call's host confirm resources.
+// The pool is created at the call's first confirmation that needs it: per-file
+// Scan batches (a few files, confirmed inline on the calling thread) never
+// start one, so the queue's up to max_inflight concurrent batches hold a lane
+// each but no idle confirm threads.
+struct CallCtx {
+  std::unique_ptr<ThreadPool> pool;
+  int nt = 1;
+  ThreadPool& get() {
+    if (!pool || pool->size() != nt) pool.reset(new ThreadPool(nt));
+    return *pool;
+  }
+};
+
+inline double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+}  // namespace tsg

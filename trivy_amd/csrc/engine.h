@@ -105,7 +105,8 @@ struct RawScan {
 struct DeviceTables;
 struct Lane;
 struct GpuOut;
-struct CallCtx;
+struct SegmentOut;     // confirm.h
+struct CallCtx;        // confirm.h
 struct K1Chain;
 struct StageIn;
 struct WireFeed;
@@ -242,8 +243,8 @@ class Engine {
   bool fold_k2_stats(Lane& ln, std::string* err);
   friend struct SegmentDriver;                           // a scan's device driver (engine.hip)
   friend struct WireFeed;                                // takes and returns the engine's packers
-  void plan_confirm(const Segment& sg, GpuOut* g) const;
-  void confirm_segment(CallCtx& cc, const Segment& sg, GpuOut& g, Secret* results, uint64_t* nconf,
+  void plan_confirm(const Segment& sg, SegmentOut* g) const;
+  void confirm_segment(CallCtx& cc, const Segment& sg, SegmentOut& g, Secret* results, uint64_t* nconf,
                        uint64_t* nfind, bool gpu_in_flight);
   Lane* acquire_lane(DeviceTables& dt, std::string* err);
   void release_lane(DeviceTables& dt, Lane* ln);
@@ -319,6 +320,9 @@ class Engine {
   // GB/s, config 1 unchanged (profiles/r6a_resident_poll.log)
   bool poll_yield_ = true;
   bool confirm_prefetch_ = true;        // confirm pool: prefetch the next file's result slot and candidate text (TSG_CONFIRM_PREFETCH)
+  // confirmations this small run on the calling thread: engine.hip's kInlineConfirm* (a K1 change that re-measures traffic may move them here)
+  size_t inline_confirm_files_ = 0;
+  uint64_t inline_confirm_bytes_ = 0;
   int pop_spin_us_ = 2000;
   uint32_t k2_hits_per_thread_ = 1;     // K2 grid: hits of the fullest region per thread (TSG_K2_HITS_PER_THREAD)
   bool k2_stats_ = false;               // TSG_K2_STATS=1: per-rule K2 counters, printed to stderr at destruction

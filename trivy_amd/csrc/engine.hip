@@ -1422,9 +1422,21 @@ uint32_t k1_chunk_for(uint64_t bytes, uint32_t lanes, int top8, bool resident) {
   return bytes <= (512ull << 20) && !resident ? 256 : 512;
 }
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
+}  // namespace
+
+}  // namespace tsg
+#include "confirm.h"   // (this file's include block belongs to K1's build hash)
+namespace tsg {
+
+namespace {
+
+// The device's candidate record and the host's (confirm.h) are one layout:
+// GpuOut::finish_copy moves the readback into std::vector<Cand> with a memcpy.
+static_assert(sizeof(CandDev) == sizeof(Cand) && alignof(CandDev) == alignof(Cand) &&
+              offsetof(CandDev, file) == offsetof(Cand, file) && offsetof(CandDev, rule) == offsetof(Cand, rule) &&
+              offsetof(CandDev, start) == offsetof(Cand, start) && sizeof(CandDev::start) == sizeof(Cand::start) &&
+              std::is_trivially_copyable<CandDev>::value && std::is_trivially_copyable<Cand>::value,
+              "CandDev and Cand must lay out alike");
 
 }  // namespace
 
@@ -1697,29 +1709,21 @@ struct Lane : LaneStreams {
 };
 
 // GPU results of one segment, handed from a device driver thread to the
-// host confirmer.
-struct GpuOut {
-  std::vector<CandDev> cands;   // (file, rule, start) candidates, unsorted
-  std::vector<uint16_t> nl;     // '\n' count per K1 chunk
-  std::vector<uint32_t> ff;     // per-file flags (fold-special content)
-  uint32_t chunk = 0;           // K1 chunk bytes of this segment (nl[] granularity)
-  // deferred copy-out (run_segment with defer_copy): the three arrays are
+// host confirmer: what the confirmer reads is the base (confirm.h), what
+// touches HIP or the lane is here.
+struct GpuOut : SegmentOut {
+  // deferred copy-out (run_segment with defer_copy): cands, ff and nl are
   // still in the lane's pinned readback buffers; finish_copy() moves them
-  // here before the lane's next readback is queued
+  // to the base before the lane's next readback is queued
   const CandDev* rb_cands = nullptr;
   const uint32_t* rb_ff = nullptr;
   const uint16_t* rb_nl = nullptr;
   size_t n_cands = 0, n_ff = 0, n_nl = 0;
   bool deferred = false;
   // device-only scans: the gather buffer (its lease ends with this record,
-  // after the confirmation), where each file's bytes are in it, and what the
-  // gather took; need / gruns / caps / guard_ok only with tsg_test_keep_gather.
-  // gbase: the buffer's host address (the CPU model sets one of its own).
+  // after the confirmation; the base's gbase is its host address);
+  // need / gruns / caps / guard_ok only with tsg_test_keep_gather.
   GatherLease gather;
-  const uint8_t* gbase = nullptr;
-  bool gathered = false;
-  uint64_t gather_total = 0, gather_files = 0;
-  std::vector<uint64_t> goff;
   std::vector<uint8_t> need;
   std::vector<GatherRun> gruns;
   std::vector<uint64_t> gather_caps;
@@ -1730,7 +1734,8 @@ struct GpuOut {
   size_t n_goff = 0, n_need = 0, n_gruns = 0;
   void finish_copy() {
     if (!deferred) return;
-    cands.assign(rb_cands, rb_cands + n_cands);
+    cands.resize(n_cands);                       // (CandDev -> Cand: the one conversion, see the static_assert)
+    if (n_cands) std::memcpy(cands.data(), rb_cands, n_cands * sizeof(Cand));
     ff.assign(rb_ff, rb_ff + n_ff);
     nl.assign(rb_nl, rb_nl + n_nl);
     if (gathered) {
@@ -1739,28 +1744,6 @@ struct GpuOut {
       gruns.assign(rb_gruns, rb_gruns + n_gruns);
     }
     deferred = false;
-  }
-  // the confirmation's plan (plan_confirm): candidates grouped per file, the
-  // files to confirm (largest first) and the rest.  (Built on the driver
-  // thread it delayed the next piece's launch by as much as it saved the
-  // confirming thread: profiles/rd4q_bench_c3prof.log; it is now built while
-  // the next piece's passes run.)
-  bool planned = false;
-  std::vector<uint32_t> per_file, work, light;
-  std::vector<CandDev> sorted;
-};
-
-// One call's host confirm resources.
-// The pool is created at the call's first confirmation that needs it: per-file
-// Scan batches (a few files, confirmed inline on the calling thread) never
-// start one, so the queue's up to max_inflight concurrent batches hold a lane
-// each but no idle confirm threads.
-struct CallCtx {
-  std::unique_ptr<ThreadPool> pool;
-  int nt = 1;
-  ThreadPool& get() {
-    if (!pool || pool->size() != nt) pool.reset(new ThreadPool(nt));
-    return *pool;
   }
 };
 
@@ -2056,6 +2039,8 @@ std::unique_ptr<Engine> Engine::create(std::shared_ptr<const Ruleset> rs, const 
   e->rs_ = std::move(rs);
   e->devices_ = devices;
   if (!build_prefilter(*e->rs_, &e->pf_, err)) return nullptr;
+  e->inline_confirm_files_ = kInlineConfirmFiles;
+  e->inline_confirm_bytes_ = kInlineConfirmBytes;
   SegmentPolicy& sp = e->seg_;
   sp.dense_files_per_gb = kDenseFilesPerGB;
   env_int("TSG_PIECES", 1, 64, &sp.pieces);
@@ -2191,21 +2176,6 @@ void Engine::release_lane(DeviceTables& dt, Lane* ln) {
   dt.free_lanes.push_back(ln);
 }
 
-CallCtx* Engine::acquire_call() {
-  std::lock_guard<std::mutex> lk(call_mu_);
-  const int nt = threads_ > 0 ? threads_ : static_cast<int>(std::min(16u, std::max(1u, std::thread::hardware_concurrency())));
-  CallCtx* cc = nullptr;
-  if (!free_calls_.empty()) {
-    cc = free_calls_.back();
-    free_calls_.pop_back();
-  } else {
-    calls_.emplace_back(new CallCtx());
-    cc = calls_.back().get();
-  }
-  cc->nt = nt;                                   // (the pool itself starts on first use: CallCtx::get)
-  return cc;
-}
-
 void Engine::footprint(uint32_t* lanes, uint32_t* calls, uint32_t* pool_threads) {
   *lanes = 0;
   for (auto& d : dev_) {
@@ -2233,92 +2203,9 @@ std::unique_ptr<Engine> Engine::create_model(std::shared_ptr<const Ruleset> rs, 
   std::unique_ptr<Engine> e(new Engine());
   e->rs_ = std::move(rs);
   e->pf_ = pf;
+  e->inline_confirm_files_ = kInlineConfirmFiles;
+  e->inline_confirm_bytes_ = kInlineConfirmBytes;
   return e;
-}
-
-bool Engine::model_scan_device(const BatchInput& in, uint32_t chunk, SecretVec* results, ScanStats* st, std::string* err,
-                               RawScan* raw, const std::function<void()>* before_confirm) {
-  if (!in.h_data || !in.offsets || !in.paths || chunk == 0) { *err = "model_scan_device: NULL argument"; return false; }
-  const uint32_t nfiles = in.nfiles;
-  const uint64_t total = nfiles ? in.offsets[nfiles] : 0;
-  // the GPU passes' outputs as the table model gives them: candidates, file
-  // flags, '\n' per chunk
-  GpuOut g;
-  g.chunk = chunk;
-  g.ff.assign(nfiles, 0);
-  g.nl.assign((total + chunk - 1) / chunk, 0);
-  for (uint64_t x = 0; x < total; ++x) g.nl[x / chunk] += in.h_data[x] == '\n';
-  bool all = false;
-  for (const auto& pr : pf_.rules) all = all || pr.mode == 1;
-  std::vector<uint8_t> need(nfiles, 0);
-  for (uint32_t f = 0; f < nfiles; ++f) {
-    std::vector<std::vector<uint64_t>> cand;
-    std::vector<uint8_t> gate;
-    if (prefilter_reference_file(pf_, in.h_data + in.offsets[f], in.offsets[f + 1] - in.offsets[f], &cand, &gate))
-      g.ff[f] = kFileFoldSpecial;
-    for (size_t r = 0; r < cand.size(); ++r)
-      for (uint64_t s : cand[r]) g.cands.push_back(CandDev{f, static_cast<uint32_t>(r), s});
-    need[f] = all || g.ff[f] || std::any_of(cand.begin(), cand.end(), [](const std::vector<uint64_t>& v) { return !v.empty(); });
-  }
-  // the gather: plan_gather's layout, the runs copied byte for byte into a
-  // buffer of exactly gather_total bytes (so a read outside a run is a read
-  // outside an allocation)
-  GatherPlan gp;
-  plan_gather(in.offsets, nfiles, 0, need.data(), chunk, &gp);
-  std::vector<uint8_t> buf(gp.total);
-  for (const GatherRun& r : gp.runs) std::memcpy(buf.data() + r.dst, in.h_data + r.src, r.len);
-  g.gbase = buf.data();
-  g.gathered = true;
-  g.gather_total = gp.total;
-  g.goff = gp.goff;
-  // the confirmation of a device-only segment: no host copy of the batch
-  Segment sg;
-  sg.in = in;
-  sg.in.h_data = nullptr;
-  sg.bytes = total;
-  if (before_confirm && *before_confirm) (*before_confirm)();    // (the caller's batch may be gone from here on)
-  results->clear();
-  results->resize(nfiles);
-  uint64_t nconf = 0, nfind = 0;
-  CallCtx* cc = acquire_call();
-  try {
-    confirm_segment(*cc, sg, g, results->data(), &nconf, &nfind, false);
-  } catch (const std::exception& x) {
-    release_call(cc);
-    *err = x.what();
-    return false;
-  }
-  release_call(cc);
-  if (st) {
-    *st = ScanStats();
-    st->bytes = total;
-    st->files = nfiles;
-    st->confirm_files = nconf;
-    st->findings = nfind;
-    st->chunk_bytes = chunk;
-    st->gather_files = g.gather_files;
-    st->gather_bytes = gp.total;
-    st->gather_runs = gp.runs.size();
-  }
-  if (raw) {
-    *raw = RawScan();
-    raw->segs.resize(1);
-    RawSegment& rec = raw->segs[0];
-    rec.nfiles = nfiles;
-    rec.bytes = total;
-    rec.chunk = chunk;
-    rec.need = need;
-    rec.goff = gp.goff;
-    rec.runs = gp.runs;
-    rec.gather_total = gp.total;
-    rec.gathered = buf;
-  }
-  return true;
-}
-
-void Engine::release_call(CallCtx* cc) {
-  std::lock_guard<std::mutex> lk(call_mu_);
-  free_calls_.push_back(cc);
 }
 
 // What the phases of one run_segment call share.
@@ -2952,7 +2839,7 @@ bool Engine::prefilter_only(const BatchInput& in, std::vector<std::vector<std::v
   const size_t nr = pf_.rules.size();   // the rules, then the exclude-block pseudo-rules
   if (cands) {
     cands->assign(in.nfiles, std::vector<std::vector<uint64_t>>(nr));
-    for (const CandDev& c : out.cands) {
+    for (const Cand& c : out.cands) {
       if (c.file >= in.nfiles || c.rule >= nr) { *err = "prefilter_only: candidate outside the batch"; return false; }
       (*cands)[c.file][c.rule].push_back(c.start);
     }
@@ -3682,298 +3569,6 @@ bool Engine::prepare_layer_tar_device(const void* d_tar, uint64_t len, const Fee
   return true;
 }
 
-// Host confirmation of one segment (files [0, in.nfiles) of sg.in, results
-// into results[0..nfiles)) from that segment's GPU output `g`.
-void Engine::plan_confirm(const Segment& sg, GpuOut* gp) const {
-  GpuOut& g = *gp;
-  const BatchInput& in = sg.in;
-  const size_t nr = rs_->rules.size();
-  // group candidates per file (counting sort by file, then sort each file's list)
-  g.per_file.assign(in.nfiles + 1, 0);
-  for (const CandDev& c : g.cands) g.per_file[c.file + 1]++;
-  for (uint32_t f = 0; f < in.nfiles; ++f) g.per_file[f + 1] += g.per_file[f];
-  g.sorted.resize(g.cands.size());
-  {
-    std::vector<uint32_t> pos(g.per_file.begin(), g.per_file.end() - 1);
-    for (const CandDev& c : g.cands) g.sorted[pos[c.file]++] = c;
-  }
-  bool any_full = false;
-  for (size_t r = 0; r < nr; ++r) if (pf_.rules[r].mode == 1) any_full = true;
-  // files to confirm (candidates, fold-special content, or host-evaluated
-  // rules), largest first (LPT: the per-file confirm cost grows with size);
-  // every other file only needs the global allow-path outcome and is handled
-  // in blocks after them (image layers: hundreds of thousands of such files)
-  g.work.clear();
-  g.light.clear();
-  g.work.reserve(in.nfiles / 4 + 16);
-  for (uint32_t f = sg.lead; f < in.nfiles; ++f) {
-    if (any_full || g.ff[f] || g.per_file[f] != g.per_file[f + 1]) g.work.push_back(f);
-    else g.light.push_back(f);
-  }
-  // largest first, by power-of-two size class (a counting sort: a full sort
-  // of config 5's 13k files per piece cost ~1 ms on the confirming thread;
-  // LPT within a factor of two balances the pool as well)
-  {
-    uint32_t cnt[65] = {};
-    auto cls = [&](uint32_t f) {
-      const uint64_t n = in.offsets[f + 1] - in.offsets[f];
-      return 63 - __builtin_clzll(n + 1);           // 0..63
-    };
-    for (uint32_t f : g.work) ++cnt[63 - cls(f) + 1];
-    for (int k = 1; k <= 64; ++k) cnt[k] += cnt[k - 1];
-    std::vector<uint32_t> by(g.work.size());
-    for (uint32_t f : g.work) by[cnt[63 - cls(f)]++] = f;
-    g.work.swap(by);
-  }
-  g.planned = true;
-}
-
-namespace {
-
-// Where the confirmer reads a segment's bytes -- the only reader of
-// BatchInput::h_data on the confirm path: the caller's host copy
-// (std::false_type), or a device-only scan's gather buffer through the
-// device's goff (std::true_type).  The confirm worker is instantiated once per
-// source, so neither pays a branch per file for the other.
-struct ConfirmBytes {
-  const uint8_t* h;
-  const uint64_t* off;
-  const uint8_t* gbuf;
-  const uint64_t* goff;
-  const uint8_t* content(std::false_type, uint32_t f) const { return h + off[f]; }
-  const uint8_t* content(std::true_type, uint32_t f) const { return gbuf + goff[f]; }
-  // K1's newline counts are per chunk of the segment's frame; prefix_at also
-  // reads the bytes between the chunk boundary below the file and the file
-  void newlines(std::false_type, uint32_t f, uint32_t, NlSource* n) const {
-    n->data = h;
-    n->file_off = off[f];
-  }
-  // (the gather starts every run on that boundary, so the head bytes are in
-  // the buffer in front of the file: no pointer outside it is formed)
-  void newlines(std::true_type, uint32_t f, uint32_t chunk, NlSource* n) const {
-    const uint64_t head = off[f] % chunk;
-    n->data = gbuf + (goff[f] - head);
-    n->data_off = off[f] - head;
-    n->file_off = off[f];
-  }
-};
-
-}  // namespace
-
-void Engine::confirm_segment(CallCtx& cc, const Segment& sg, GpuOut& g, Secret* results, uint64_t* nconf_out,
-                             uint64_t* nfind_out, bool gpu_in_flight) {
-  const BatchInput& in = sg.in;
-  const Ruleset& rs = *rs_;
-  const size_t nplan = pf_.rules.size();   // rules + exclude-block pseudo-rules
-  const auto t_begin = std::chrono::steady_clock::now();
-  if (!g.planned) plan_confirm(sg, &g);
-  const ConfirmBytes src{in.h_data, in.offsets, g.gbase, g.goff.data()};
-  if (g.gathered) {
-    // a file to confirm that the device did not gather (or placed outside
-    // what it gathered) fails the call: it is never scanned from wrong bytes
-    if (g.goff.size() != in.nfiles || (!g.gbase && g.gather_total)) throw std::runtime_error("device-only scan: no gather for the segment");
-    for (uint32_t f : g.work) {
-      const uint64_t o = g.goff[f], head = in.offsets[f] % g.chunk;
-      if (o == kGatherNone || o < head || o > g.gather_total || in.offsets[f + 1] - in.offsets[f] > g.gather_total - o)
-        throw std::runtime_error("device-only scan: a file the confirmer reads was not gathered");
-    }
-    uint64_t nf = 0;
-    for (uint32_t f = sg.lead; f < in.nfiles; ++f) nf += g.goff[f] != kGatherNone;
-    g.gather_files = nf;
-  } else if (!in.h_data && !g.work.empty()) {
-    throw std::runtime_error("scan without a host copy of the batch and without a gather");
-  }
-  const std::vector<uint32_t>& per_file = g.per_file;
-  std::vector<CandDev>& sorted = g.sorted;
-  const std::vector<uint32_t>& work = g.work;
-  const std::vector<uint32_t>& light = g.light;
-  // the plan every confirmed file starts from, and its mode-1 rules
-  std::vector<uint8_t> kind0(nplan, kPlanNoMatch);
-  std::vector<uint32_t> full_rules;
-  for (size_t r = 0; r < nplan; ++r) {
-    if (pf_.rules[r].mode == 1) {            // (mode 3: only with a presence candidate)
-      kind0[r] = kPlanFull;
-      full_rules.push_back(static_cast<uint32_t>(r));
-    }
-  }
-  results -= sg.lead;                      // results[f] for the piece's files f >= lead
-  constexpr uint32_t kLightBlock = 512;
-  const uint32_t nlight_blocks = static_cast<uint32_t>((light.size() + kLightBlock - 1) / kLightBlock);
-  std::atomic<uint32_t> next_light{0};
-  std::atomic<uint32_t> next{0};
-  std::atomic<uint64_t> nfind{0}, nconf{0};
-  // TSG_HOST_PROFILE: worker thread-ns in the plan (candidates sorted and
-  // grouped), scan_file and storing the result
-  std::atomic<uint64_t> ph_plan{0}, ph_scan{0}, ph_store{0};
-  const bool prof = host_profile_;
-  auto light_files = [&]() {
-    for (;;) {
-      const uint32_t b = next_light.fetch_add(1);
-      if (b >= nlight_blocks) break;
-      const size_t e = std::min<size_t>(light.size(), (static_cast<size_t>(b) + 1) * kLightBlock);
-      for (size_t k = static_cast<size_t>(b) * kLightBlock; k < e; ++k) {
-        const uint32_t f = light[k];
-        if (confirm_prefetch_ && k + 8 < e) __builtin_prefetch(in.paths[light[k + 8]]);   // (path strings: scattered)
-        // no candidates, no host-evaluated rule: only the global allow-path outcome remains
-        const char* p = in.paths[f];
-        const size_t pn = in.path_lens ? in.path_lens[f] : std::strlen(p);
-        if (global_allow_path(rs, reinterpret_cast<const uint8_t*>(p), pn)) results[f] = Secret::path_only(p, pn);
-      }
-    }
-  };
-  auto worker = [&](auto from) {               // from: where the bytes are (ConfirmBytes)
-    FilePlan plan;
-    std::vector<std::vector<uint64_t>> spare;
-    // per-thread counts and work taken a few files at a time: 15 threads
-    // hitting shared counters once per file serialised on their cache lines
-    uint64_t my_conf = 0, my_find = 0, my_plan = 0, my_scan = 0, my_store = 0;
-    constexpr uint32_t kTake = 4;
-    uint32_t wi = 0, wend = 0;
-    for (;;) {
-      if (wi == wend) {
-        wi = next.fetch_add(kTake);
-        if (wi >= work.size()) break;
-        wend = std::min<uint32_t>(wi + kTake, static_cast<uint32_t>(work.size()));
-      }
-      uint32_t f = work[wi++];
-      if (confirm_prefetch_ && wi < wend) {
-        // the next file of this take: its result slot and the text at its
-        // first candidate starts, fetched while this file is confirmed (the
-        // host has not touched the batch's bytes since they were written):
-        // resident config 5 602-611 -> 614-657 GB/s (profiles/r6j_confirm_prefetch_c5.log; two files
-        // ahead and a wider window were no better)
-        const uint32_t fn = work[wi];
-        __builtin_prefetch(results + fn, 1);
-        __builtin_prefetch(in.paths[fn]);
-        const uint8_t* cn = src.content(from, fn);
-        const uint64_t ln = in.offsets[fn + 1] - in.offsets[fn];
-        for (uint32_t k = per_file[fn], ke = std::min(per_file[fn + 1], per_file[fn] + 4); k < ke; ++k) {
-          const uint64_t st = sorted[k].start;
-          if (st < ln) {
-            __builtin_prefetch(cn + st);
-            if (st + 64 < ln) __builtin_prefetch(cn + st + 64);
-          }
-        }
-      }
-      const auto tp0 = prof ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
-      const char* path_p = in.paths[f];
-      const size_t path_n = in.path_lens ? in.path_lens[f] : std::strlen(path_p);
-      const uint8_t* content = src.content(from, f);
-      const size_t len = in.offsets[f + 1] - in.offsets[f];
-      const bool binary = in.binary ? in.binary[f] != 0 : false;
-      const uint32_t cb = per_file[f], ce = per_file[f + 1];
-      if (g.ff[f]) {
-        // fold-special file (U+0130/U+212A/U+017F present): the two passes run
-        // on the host with the variant scan DFA, then the exact confirmer
-        ++my_conf;
-        std::vector<std::vector<uint64_t>> vc;
-        std::vector<uint8_t> vg;
-        prefilter_variant_file(pf_, content, len, &vc, &vg);
-        plan_from_candidates(pf_, &vc, &plan);
-        Secret s = scan_file(rs, path_p, path_n, content, len, binary, &plan);
-        my_find += s.findings().size();
-        results[f] = std::move(s);
-        continue;
-      }
-      ++my_conf;
-      plan.kind = kind0;                       // mode-1 rules kPlanFull, the rest kPlanNoMatch
-      for (RuleCandidates& c : plan.cands) {   // start lists are reused from file to file
-        c.starts.clear();
-        spare.push_back(std::move(c.starts));
-      }
-      plan.cands.clear();
-      std::sort(sorted.begin() + cb, sorted.begin() + ce, [](const CandDev& a, const CandDev& b) {
-        return a.rule != b.rule ? a.rule < b.rule : a.start < b.start;
-      });
-      for (uint32_t k = cb; k < ce;) {
-        uint32_t r = sorted[k].rule;
-        RuleCandidates rc;
-        rc.rule = r;
-        if (!spare.empty()) {
-          rc.starts = std::move(spare.back());
-          spare.pop_back();
-        }
-        while (k < ce && sorted[k].rule == r) {
-          if (rc.starts.empty() || rc.starts.back() != sorted[k].start) rc.starts.push_back(sorted[k].start);
-          ++k;
-        }
-        // mode 3 presence candidates, and a mode-4 walk that gave up
-        // (kFullScanStart sorts last): the rule in full on the host
-        plan.kind[r] = pf_.rules[r].mode == 3 || rc.starts.back() == kFullScanStart ? kPlanFull
-                     : pf_.rules[r].gate_on_gpu ? kPlanCandidates : kPlanCandHostGate;
-        plan.cands.push_back(std::move(rc));
-      }
-      // the rules scan_file visits: mode-1 rules and those with candidates, ascending
-      plan.active.clear();
-      plan.active_set = true;
-      {
-        size_t a = 0, b = 0;
-        while (a < full_rules.size() || b < plan.cands.size()) {
-          const uint32_t x = a < full_rules.size() ? full_rules[a] : UINT32_MAX;
-          const uint32_t y = b < plan.cands.size() ? plan.cands[b].rule : UINT32_MAX;
-          if (x <= y) { plan.active.push_back(x); ++a; if (x == y) ++b; }
-          else { plan.active.push_back(y); ++b; }
-        }
-      }
-      NlSource nls;
-      nls.chunk_nl = g.nl.data();
-      src.newlines(from, f, g.chunk, &nls);
-      nls.chunk = g.chunk;
-      const auto tp1 = prof ? std::chrono::steady_clock::now() : tp0;
-      Secret s = scan_file(rs, path_p, path_n, content, len, binary, &plan, &nls);
-      const auto tp2 = prof ? std::chrono::steady_clock::now() : tp0;
-      my_find += s.findings().size();
-      results[f] = std::move(s);
-      if (prof) {
-        const auto tp3 = std::chrono::steady_clock::now();
-        my_plan += std::chrono::duration_cast<std::chrono::nanoseconds>(tp1 - tp0).count();
-        my_scan += std::chrono::duration_cast<std::chrono::nanoseconds>(tp2 - tp1).count();
-        my_store += std::chrono::duration_cast<std::chrono::nanoseconds>(tp3 - tp2).count();
-      }
-    }
-    nconf.fetch_add(my_conf);
-    nfind.fetch_add(my_find);
-    if (prof) { ph_plan += my_plan; ph_scan += my_scan; ph_store += my_store; }
-  };
-  // small confirmations (a few files, little text: per-file Scan batches) run
-  // on this thread; waking the pool costs more than the work
-  uint64_t work_bytes = 0;
-  for (size_t k = 0; k < work.size() && work_bytes <= kInlineConfirmBytes; ++k)
-    work_bytes += in.offsets[work[k] + 1] - in.offsets[work[k]];
-  const bool inline_confirm = work.size() <= kInlineConfirmFiles && work_bytes <= kInlineConfirmBytes &&
-                              light.size() <= kLightBlock;
-  const int nt = inline_confirm ? 1 : cc.get().size();
-  // while GPU passes are in flight one core stays with each thread driving
-  // them (a preempted driver thread stalls its GPU)
-  const int active = gpu_in_flight && nt > 1 ? nt - 1 : nt;
-  const double t_setup = ms_since(t_begin);
-  std::atomic<uint64_t> work_us{0}, light_us{0};
-  auto body = [&](int idx) {
-    if (idx >= active) return;
-    auto a = std::chrono::steady_clock::now();
-    if (g.gathered) worker(std::true_type());
-    else worker(std::false_type());
-    auto b = std::chrono::steady_clock::now();
-    light_files();
-    work_us.fetch_add(std::chrono::duration_cast<std::chrono::microseconds>(b - a).count());
-    light_us.fetch_add(std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - b).count());
-  };
-  if (inline_confirm) body(0);
-  else cc.get().run(body);
-  if (host_profile_) {
-    uint64_t ph[5];
-    for (int k = 0; k < 5; ++k) ph[k] = g_scan_prof[k].exchange(0);
-    std::fprintf(stderr, "[tsg host] files %u (work %zu, light %zu) cands %zu: setup %.2f ms, wall %.2f ms, "
-                 "work %.1f + light %.1f thread-ms on %d threads (plan %.1f, scan_file %.1f, store %.1f); scan_file "
-                 "thread-ms: keywords %.1f, find %.1f, blocks %.1f, findings %.1f, sort %.1f\n", in.nfiles,
-                 work.size(), light.size(), g.cands.size(), t_setup, ms_since(t_begin), work_us.load() / 1e3,
-                 light_us.load() / 1e3, active, ph_plan.load() / 1e6, ph_scan.load() / 1e6, ph_store.load() / 1e6,
-                 ph[0] / 1e6, ph[1] / 1e6, ph[2] / 1e6, ph[3] / 1e6, ph[4] / 1e6);
-  }
-  *nconf_out += nconf.load();
-  *nfind_out += nfind.load();
-}
-
 struct ScanJob {
   size_t seg = 0;
   GpuOut out;
@@ -4001,7 +3596,7 @@ void record_raw_segment(const Segment& sg, const ScanJob& job, size_t nrules, Ra
   if (sg.lead) rec.lead_flags = g.ff[0];
   for (uint32_t f = sg.lead; f < sg.in.nfiles; ++f) raw->ff[sg.f0 + f - sg.lead] = g.ff[f];
   std::vector<std::pair<uint32_t, uint64_t>> lead;
-  for (const CandDev& c : g.cands) {
+  for (const Cand& c : g.cands) {
     if (c.file >= sg.in.nfiles || c.rule >= nrules) { raw->error = "raw outputs: candidate outside the segment"; return; }
     if (c.file < sg.lead) { lead.emplace_back(c.rule, c.start); continue; }
     auto& per_rule = raw->cands[sg.f0 + c.file - sg.lead];
