@@ -166,7 +166,7 @@ int tsg_scan_batch_resident(tsg_engine* e, const void* d_data, const uint8_t* h_
                             const uint64_t* offsets, uint32_t nfiles, const char* const* paths,
                             const uint32_t* path_lens, const uint8_t* binary, tsg_result** out);
 /* The device-only scan: the batch exists only in HBM (the output of
- * tsg_strip_cr_device, a GPU decompressor, a peer-to-peer read) and no host
+ * tsg_strip_cr_device, tsg_inflate_gzip_device, a peer-to-peer read) and no host
  * copy is passed.  d_data: as for tsg_scan_batch_resident (16-byte aligned,
  * readable for 16 bytes past the end, on one of the engine's devices);
  * offsets, paths, path_lens, binary: host arrays as above.  After its second
@@ -320,8 +320,8 @@ int tsg_prepare_batch_device(tsg_engine* e, const void* d_raw, const uint64_t* r
 /* tsg_prepare_layer_tar with feed options. */
 int tsg_prepare_layer_tar_opts(const tsg_ruleset* rs, const uint8_t* tar, size_t len, const tsg_feed_opts* opts,
                                tsg_prepared** out);
-/* tsg_prepare_layer_tar_opts for a layer tar that lives in HBM (what a GPU
- * decompressor or a peer-to-peer read delivers for an image scan): the first
+/* tsg_prepare_layer_tar_opts for a layer tar that lives in HBM (what
+ * tsg_inflate_gzip_device or a peer-to-peer read delivers for an image scan): the first
  * link of
  *   tsg_prepare_layer_tar_device -> tsg_scan_batch_device,
  * walker.LayerTar.Walk (pkg/fanal/walker/tar.go:35-103) included.  d_tar: len
@@ -367,6 +367,57 @@ int tsg_prepare_layer_tar_device(tsg_engine* e, const void* d_tar, uint64_t len,
  * TSG_ERR_INVALID for a tsg_prepared of another call. */
 int tsg_prepared_tar_stats(const tsg_prepared* p, uint64_t* blocks, uint64_t* marked, uint64_t* gathered_bytes,
                            uint32_t* fallback_reads, uint32_t* retries, double* scan_ms);
+/* ---- gzip layers inflated on the GPU ----
+ * Every layer an image scan receives is a gzip stream, which the reference
+ * opens with layer.Uncompressed() (pkg/fanal/artifact/image/image.go:464-492)
+ * -- Go's compress/gzip over compress/flate -- before walker.LayerTar.Walk.
+ * tsg_inflate_gzip_device is that step for a batch of streams that lies in
+ * HBM, and the first link of
+ *   tsg_inflate_gzip_device -> tsg_prepare_layer_tar_device -> tsg_scan_batch_device:
+ * only the compressed bytes and the confirmer's gather cross the link.
+ * Stream i is d_gz[gz_offsets[i], gz_offsets[i + 1]) and inflates into the
+ * slot d_dst[dst_offsets[i], dst_offsets[i + 1]); gz_offsets, dst_offsets
+ * (nstreams + 1 each, nondecreasing), out_lens and status (nstreams each) are
+ * host arrays.  d_gz and d_dst are 16-byte aligned device memory of one
+ * device, do not overlap, and every slot starts 16-byte aligned; aligned
+ * 16-byte loads may touch up to 16 bytes past d_gz's last stream (the d_data
+ * convention above), but nothing past a stream's own end influences its
+ * result, and nothing outside a stream's slot is written, whatever the input.
+ * One wavefront inflates one stream, the longest streams starting first: the
+ * call is parallel across streams, not inside one.  RFC 1952 over RFC 1951
+ * as compress/gzip reads it: all members of a stream are inflated one behind
+ * the other (multistream), FEXTRA / FNAME / FCOMMENT are skipped, FHCRC and
+ * every member's CRC32 and ISIZE are checked; bytes behind the last member
+ * are read as another header, so zero padding is an error.  status[i]:
+ *   TSG_INFLATE_OK
+ *   TSG_INFLATE_HEADER     "gzip: invalid header"
+ *   TSG_INFLATE_CORRUPT    "flate: corrupt input" (Go adds an offset; not reproduced)
+ *   TSG_INFLATE_EOF        "unexpected EOF"
+ *   TSG_INFLATE_CHECKSUM   "gzip: invalid checksum"
+ *   TSG_INFLATE_DST_FULL   the output did not fit the slot: call again with a larger one
+ * -- the first error in stream order.  out_lens[i] = the bytes written to
+ * slot i (for a failed stream, up to where the decoder stopped).  Returns
+ * TSG_OK when every stream is TSG_INFLATE_OK, else TSG_ERR_INVALID with the
+ * first failing stream's index and text in tsg_last_error(); status[] and
+ * out_lens[] are filled either way, and a good stream's output is valid when
+ * its neighbour fails.  *ms (may be NULL) = kernel time.  Synchronous; runs
+ * on the device that holds d_gz. */
+enum {
+  TSG_INFLATE_OK = 0,
+  TSG_INFLATE_HEADER = 1,
+  TSG_INFLATE_CORRUPT = 2,
+  TSG_INFLATE_EOF = 3,
+  TSG_INFLATE_CHECKSUM = 4,
+  TSG_INFLATE_DST_FULL = 5
+};
+int tsg_inflate_gzip_device(tsg_engine* e, const void* d_gz, const uint64_t* gz_offsets, uint32_t nstreams,
+                            void* d_dst, const uint64_t* dst_offsets, uint64_t* out_lens, int32_t* status, double* ms);
+/* Go's error text of a status ("" for TSG_INFLATE_OK and TSG_INFLATE_DST_FULL) */
+const char* tsg_inflate_status_text(int32_t status);
+/* ISIZE of the last member of a gzip stream in host memory: the inflated size
+ * mod 2^32 of that member alone -- a hint for the slot's size, no more.
+ * TSG_ERR_INVALID when gz does not start like a gzip stream. */
+int tsg_gzip_size_hint(const uint8_t* gz, size_t len, uint64_t* isize);
 /* `trivy fs` over a directory tree on disk: walker.FS.Walk (pkg/fanal/walker/
  * fs.go:25-97; filepath.WalkDir order, symlinks not followed, defaultSkipDirs
  * **\/.git proc sys dev, permission errors ignored), AnalyzeFile's gate before

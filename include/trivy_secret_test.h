@@ -372,6 +372,21 @@ int tsg_queue_create_model(const tsg_ruleset* rs, uint32_t max_files, uint64_t m
  * not come. */
 int tsg_queue_timeouts(tsg_queue* q, uint64_t* timeouts);
 
+/* The CPU model of tsg_inflate_gzip_device (inflate.h's inflate_model): the
+ * same arguments with gz and dst in host memory and e unused (may be NULL);
+ * status[] and out_lens[] are what the device call gives.  Nothing outside a
+ * stream's slot is written. */
+int tsg_test_inflate_model(tsg_engine* e, const void* gz, const uint64_t* gz_offsets, uint32_t nstreams, void* dst,
+                           const uint64_t* dst_offsets, uint64_t* out_lens, int32_t* status, double* ms);
+/* The checksum pass on the CPU: the CRC32 of data[0, len) taken in slices of
+ * *slice bytes (crc32_slices) and folded with the shift operator
+ * (crc32_combine); *nslices = the slices taken.  Any out pointer may be NULL. */
+int tsg_test_crc32_slices(const uint8_t* data, uint64_t len, uint32_t* crc, uint32_t* slice, uint64_t* nslices);
+/* The kernel times of the calling thread's last tsg_inflate_gzip_device call
+ * (tools/inflate_probe.py): the inflate and the checksum kernel in ms, the
+ * members it found and the slices it summed.  Any pointer may be NULL. */
+int tsg_test_inflate_last_stats(double* inflate_ms, double* crc_ms, uint64_t* members, uint64_t* slices);
+
 #ifdef __cplusplus
 }
 #endif

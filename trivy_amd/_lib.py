@@ -247,6 +247,24 @@ SIGNATURES += [
                                                           ctypes.POINTER(ctypes.c_void_p)]),
 ]
 
+SIGNATURES += [
+    ("tsg_inflate_gzip_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.POINTER(ctypes.c_double)]),
+    ("tsg_inflate_status_text", ctypes.c_char_p, [ctypes.c_int32]),
+    ("tsg_gzip_size_hint", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64)]),
+    ("tsg_test_inflate_model", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.POINTER(ctypes.c_double)]),
+    ("tsg_test_crc32_slices", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32),
+                                             ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)]),
+    ("tsg_test_inflate_last_stats", ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                                   ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+]
+
+# per-stream status of tsg_inflate_gzip_device
+INFLATE_OK, INFLATE_HEADER, INFLATE_CORRUPT, INFLATE_EOF, INFLATE_CHECKSUM, INFLATE_DST_FULL = range(6)
+
 # tsg_read_fn: int64_t (*)(void* user, uint8_t* buf, size_t cap)
 READ_FN = ctypes.CFUNCTYPE(ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
 

@@ -21,6 +21,7 @@
 #include "engine.h"
 #include "gosort.h"
 #include "guard.h"
+#include "inflate_dev.h"
 #include "feed.h"
 #include "tar.h"
 #include "tarscan.h"
@@ -1755,6 +1756,84 @@ int tsg_prepare_layer_tar_device_model(const tsg_ruleset* rs, const uint8_t* tar
   *out = p.release();
   return TSG_OK;
   TSG_API_CATCH
+}
+
+static_assert(TSG_INFLATE_OK == kInfOk && TSG_INFLATE_HEADER == kInfHeader && TSG_INFLATE_CORRUPT == kInfCorrupt &&
+                  TSG_INFLATE_EOF == kInfEof && TSG_INFLATE_CHECKSUM == kInfChecksum && TSG_INFLATE_DST_FULL == kInfDstFull,
+              "inflate.h and trivy_secret.h number the statuses alike");
+
+namespace {
+thread_local InflateStats g_inflate_stats;
+// TSG_OK, or TSG_ERR_INVALID naming the first stream that is not TSG_INFLATE_OK
+int inflate_verdict(const int32_t* status, uint32_t nstreams) {
+  for (uint32_t i = 0; i < nstreams; ++i) {
+    if (status[i] == kInfOk) continue;
+    const char* text = status[i] == kInfDstFull ? "the output does not fit its slot" : inflate_status_text(status[i]);
+    return fail(TSG_ERR_INVALID, "gzip stream " + std::to_string(i) + ": " + text);
+  }
+  return TSG_OK;
+}
+}  // namespace
+
+int tsg_inflate_gzip_device(tsg_engine* e, const void* d_gz, const uint64_t* gz_offsets, uint32_t nstreams,
+                            void* d_dst, const uint64_t* dst_offsets, uint64_t* out_lens, int32_t* status, double* ms) {
+  TSG_API_TRY
+  if (!e || (nstreams && (!gz_offsets || !dst_offsets || !out_lens || !status))) return fail(TSG_ERR_INVALID, "NULL argument");
+  if (ms) *ms = 0;
+  std::string err;
+  InflateStats st;
+  if (!inflate_gzip_device(d_gz, gz_offsets, nstreams, d_dst, dst_offsets, out_lens, status, &st, &err))
+    return fail(err.find("inflate:") == 0 ? TSG_ERR_INVALID : TSG_ERR_HIP, err);
+  g_inflate_stats = st;
+  if (ms) *ms = st.inflate_ms + st.crc_ms;
+  return inflate_verdict(status, nstreams);
+  TSG_API_CATCH
+}
+
+const char* tsg_inflate_status_text(int32_t status) { return inflate_status_text(status); }
+
+int tsg_gzip_size_hint(const uint8_t* gz, size_t len, uint64_t* isize) {
+  TSG_API_TRY
+  if (!gz || !isize) return fail(TSG_ERR_INVALID, "NULL argument");
+  if (!gzip_size_hint(gz, len, isize)) return fail(TSG_ERR_INVALID, "not a gzip stream");
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_test_inflate_model(tsg_engine*, const void* gz, const uint64_t* gz_offsets, uint32_t nstreams, void* dst,
+                           const uint64_t* dst_offsets, uint64_t* out_lens, int32_t* status, double* ms) {
+  TSG_API_TRY
+  if (nstreams && (!gz_offsets || !dst_offsets || !out_lens || !status)) return fail(TSG_ERR_INVALID, "NULL argument");
+  if (ms) *ms = 0;
+  for (uint32_t i = 0; i < nstreams; ++i) {
+    if (gz_offsets[i] > gz_offsets[i + 1] || dst_offsets[i] > dst_offsets[i + 1])
+      return fail(TSG_ERR_INVALID, "inflate: offsets must not decrease");
+    const uint8_t* src = static_cast<const uint8_t*>(gz) + gz_offsets[i];
+    status[i] = inflate_model([src](uint64_t k) { return static_cast<uint32_t>(src[k]); }, gz_offsets[i + 1] - gz_offsets[i],
+                              static_cast<uint8_t*>(dst) + dst_offsets[i], dst_offsets[i + 1] - dst_offsets[i], &out_lens[i]);
+  }
+  return inflate_verdict(status, nstreams);
+  TSG_API_CATCH
+}
+
+int tsg_test_crc32_slices(const uint8_t* data, uint64_t len, uint32_t* crc, uint32_t* slice, uint64_t* nslices) {
+  TSG_API_TRY
+  if (len && !data) return fail(TSG_ERR_INVALID, "NULL argument");
+  std::vector<uint32_t> s(crc32_nslices(len));
+  crc32_slices(data, len, s.data());
+  if (crc) *crc = crc32_combine(s.data(), len);
+  if (slice) *slice = kCrcSlice;
+  if (nslices) *nslices = s.size();
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_test_inflate_last_stats(double* inflate_ms, double* crc_ms, uint64_t* members, uint64_t* slices) {
+  if (inflate_ms) *inflate_ms = g_inflate_stats.inflate_ms;
+  if (crc_ms) *crc_ms = g_inflate_stats.crc_ms;
+  if (members) *members = g_inflate_stats.members;
+  if (slices) *slices = g_inflate_stats.slices;
+  return TSG_OK;
 }
 
 int tsg_prepare_fs_tree(const tsg_ruleset* rs, const char* root, const tsg_feed_opts* opts, tsg_prepared** out) {

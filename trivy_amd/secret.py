@@ -295,6 +295,150 @@ class Scanner:
         finally:
             L.tsg_prepared_free(h)
 
+    def InflateGzipDevice(self, d_gz, gz_offsets, caps=None, hints=None, max_regrow=9, with_stats=False):
+        """A batch of gzip streams that lies in HBM, inflated there
+        (tsg_inflate_gzip_device): layer.Uncompressed() of
+        pkg/fanal/artifact/image/image.go:464-492 -- Go's compress/gzip,
+        multistream -- for all layers at once, one wavefront per stream.
+
+        d_gz: uint8 device tensor (16-byte aligned, 16 readable bytes behind
+        the last stream); gz_offsets: nstreams + 1 host integers, stream i =
+        d_gz[gz_offsets[i]:gz_offsets[i + 1]].  caps: each stream's slot size;
+        default max(size hint, 4 * compressed length) + 64, rounded up to 16
+        bytes, where the size hint is the last member's ISIZE (hints: the
+        caller's, else read from d_gz: four bytes per stream cross the link).
+        A stream whose output does not fit (TSG_INFLATE_DST_FULL) is run again
+        in a slot twice as large, at most max_regrow times; only those streams
+        run again, the others' outputs are copied on the device.
+
+        Returns (d_dst, dst_offsets, out_lens, status): stream i's output is
+        d_dst[dst_offsets[i]:dst_offsets[i] + out_lens[i]], status[i] its
+        TSG_INFLATE_* value (_lib.INFLATE_OK ...; the text:
+        tsg_inflate_status_text).  A failed stream raises nothing here: its
+        neighbours' outputs are valid.  with_stats appends {"ms": kernel time,
+        "rounds": launches after the first}."""
+        import torch
+        L = _lib.lib()
+        go = np.ascontiguousarray(gz_offsets, dtype=np.uint64)
+        n = len(go) - 1
+        if n < 0:
+            raise ValueError("gz_offsets must hold at least one entry")
+        if d_gz.dtype != torch.uint8 or not d_gz.is_cuda or not d_gz.is_contiguous() or d_gz.data_ptr() & 15:
+            raise ValueError("d_gz must be a contiguous, 16-byte aligned uint8 device tensor")
+        if n and d_gz.numel() < int(go[-1]):
+            raise ValueError("d_gz is shorter than the batch")
+        clen = (go[1:] - go[:-1]).astype(np.int64)
+        if caps is None:
+            if hints is None:
+                hints = np.zeros(n, np.int64)
+                big = np.flatnonzero(clen >= 18)
+                if len(big):
+                    at = torch.from_numpy((go[1:][big].astype(np.int64) - 4)[:, None] + np.arange(4)).to(d_gz.device)
+                    tail = d_gz[at].cpu().numpy().astype(np.int64)
+                    hints[big] = tail[:, 0] | tail[:, 1] << 8 | tail[:, 2] << 16 | tail[:, 3] << 24
+            caps = np.maximum(np.asarray(hints, np.int64), 4 * clen) + 64
+        caps = (np.asarray(caps, np.int64) + 15) & ~15 if n else np.zeros(0, np.int64)
+        if len(caps) != n:
+            raise ValueError("caps must hold one entry per stream")
+        status = np.full(n, _lib.INFLATE_DST_FULL, np.int32)
+        out_lens = np.zeros(n, np.uint64)
+        dst, do, ms, rounds = None, None, 0.0, 0
+        torch.cuda.current_stream(d_gz.device).synchronize()     # the call runs on its own stream
+        while True:
+            new_do = np.zeros(n + 1, np.uint64)
+            np.cumsum(caps, out=new_do[1:])
+            new = torch.empty(max(int(new_do[-1]), 16) + 16, dtype=torch.uint8, device=d_gz.device)
+            todo = np.flatnonzero(status == _lib.INFLATE_DST_FULL)
+            if dst is not None:                  # what is done moves over on the device
+                for i in np.flatnonzero(status != _lib.INFLATE_DST_FULL):
+                    k = int(out_lens[i])
+                    new[int(new_do[i]):int(new_do[i]) + k] = dst[int(do[i]):int(do[i]) + k]
+                torch.cuda.current_stream(d_gz.device).synchronize()
+            dst, do = new, new_do
+            runs = np.split(todo, np.flatnonzero(np.diff(todo) != 1) + 1) if len(todo) else []
+            for run in runs:                     # adjacent streams go in one launch
+                a, b = int(run[0]), int(run[-1]) + 1
+                g, d = np.ascontiguousarray(go[a:b + 1]), np.ascontiguousarray(do[a:b + 1])
+                t = ctypes.c_double()
+                rc = L.tsg_inflate_gzip_device(self.engine(), ctypes.c_void_p(d_gz.data_ptr()), g.ctypes.data, b - a,
+                                               ctypes.c_void_p(dst.data_ptr()), d.ctypes.data,
+                                               out_lens[a:b].ctypes.data, status[a:b].ctypes.data, ctypes.byref(t))
+                if rc != 0 and not L.tsg_last_error().startswith(b"gzip stream "):
+                    _lib.check(rc)               # the call itself failed, not a stream
+                ms += t.value
+            full = status == _lib.INFLATE_DST_FULL
+            if not full.any() or rounds >= max_regrow:
+                break
+            rounds += 1
+            caps = np.where(full, caps * 2, caps)
+        out = (dst, do, out_lens, status)
+        return out + ({"ms": ms, "rounds": rounds},) if with_stats else out
+
+    def ScanLayersGzipDevice(self, blobs, skip_files=(), skip_dirs=(), file_patterns=(), config_path="",
+                             with_stats=False, contents=False):
+        """The layers of an image as the registry or `docker save` hands them
+        over -- one gzip stream each -- scanned with only the compressed bytes
+        and the confirmer's gather crossing the link:
+
+            one upload of all blobs -> InflateGzipDevice (one launch for all
+            layers) -> per layer PrepareLayerTarDevice -> ScanBatchDevice
+
+        blobs: a list of bytes-like objects (bytes, or pinned buffers such as a
+        pinned uint8 torch tensor or a numpy view of one).  Returns, per
+        layer, what PrepareLayerTar(scanner, tar, ..., scan=True) returns for
+        the gunzipped tar: (ScanArgs list, walk dict, [types.Secret]) -- except
+        that the prepared contents stay on the device: ScanArgs.Content is
+        None unless contents=True downloads them.  A layer that does not
+        inflate raises WalkError with its index and Go's text
+        ("unexpected EOF", "gzip: invalid checksum", ...); a malformed tar
+        raises WalkError as PrepareLayerTarDevice does.  with_stats appends
+        {"gz_bytes", "tar_bytes", "inflate_ms", "inflate_rounds"} to the list's
+        tuple: (layers, stats)."""
+        import torch
+        L = _lib.lib()
+        views = [b.numpy() if isinstance(b, torch.Tensor) else np.frombuffer(b, dtype=np.uint8) for b in blobs]
+        n = len(views)
+        go = np.zeros(n + 1, np.uint64)
+        if n:
+            np.cumsum([len(v) for v in views], out=go[1:])
+        hints = np.zeros(n, np.int64)
+        for i, v in enumerate(views):
+            h = ctypes.c_uint64()
+            if len(v) and L.tsg_gzip_size_hint(v.ctypes.data, len(v), ctypes.byref(h)) == 0:
+                hints[i] = h.value
+        dev = torch.device("cuda", 0 if self._device == "all" else int(self._device))
+        host = torch.empty(int(go[-1]) + 16, dtype=torch.uint8).pin_memory()
+        hv = host.numpy()
+        for i, v in enumerate(views):
+            hv[int(go[i]):int(go[i + 1])] = v
+        hv[int(go[-1]):] = 0
+        d_gz = host.to(dev, non_blocking=True)   # the one upload
+        dst, do, out_lens, status, ist = self.InflateGzipDevice(d_gz, go, hints=hints, with_stats=True)
+        for i in range(n):
+            if status[i] != _lib.INFLATE_OK:
+                text = L.tsg_inflate_status_text(int(status[i])).decode() or "the inflated layer does not fit its slot"
+                raise WalkError("layer %d: %s" % (i, text))
+        layers = []
+        for i in range(n):
+            k = int(out_lens[i])
+            d_tar = dst[int(do[i]):int(do[i + 1])]
+            p_dst, offs, scan_paths, binf, walk, _ms = self.PrepareLayerTarDevice(
+                d_tar, k, skip_files=skip_files, skip_dirs=skip_dirs, file_patterns=file_patterns, config_path=config_path)
+            secrets = self.ScanBatchDevice(p_dst, offs, scan_paths, binf)
+            data = p_dst[:int(offs[-1])].cpu().numpy().tobytes() if contents and len(scan_paths) else None
+            args = [ScanArgs(p, data[int(offs[j]):int(offs[j + 1])] if data is not None else (b"" if contents else None),
+                             bool(binf[j])) for j, p in enumerate(scan_paths)]
+            layers.append((args, walk, secrets))
+        if with_stats:
+            return layers, {"gz_bytes": int(go[-1]), "tar_bytes": int(out_lens.sum()), "inflate_ms": ist["ms"],
+                            "inflate_rounds": ist["rounds"]}
+        return layers
+
+    def ScanLayerGzipDevice(self, blob, **kw):
+        """ScanLayersGzipDevice for one layer: (ScanArgs list, walk dict, [types.Secret])."""
+        kw.pop("with_stats", None)
+        return self.ScanLayersGzipDevice([blob], **kw)[0]
+
     def Scan(self, args):
         return self.ScanBatch([args])[0]
 
