@@ -291,6 +291,20 @@ int tsg_test_plan_segments(const uint64_t* offsets, uint32_t nfiles, int residen
 int tsg_test_plan_wire_strips(uint64_t segment_bytes, uint64_t strip, int first_segment, int npackers,
                               uint64_t* offsets, uint64_t* bytes, uint32_t cap, uint32_t* nout);
 
+/* K1's work-item schedule as the host restates it (csrc/k1_schedule.h; the
+ * kernel, tsg_k1_scan_v3, keeps its own arithmetic) for a launch of nchunks
+ * chunks on a grid of `blocks` workgroups of 16 waves with `rounds` tail
+ * rounds (TSG_K1_TAIL_ROUNDS) and, top8 != 0, the 8-chunk bulk level: no
+ * engine, no device.  levels[0..5] = the chunks of the 8-, 4-, 2- and 1-chunk
+ * levels (in batch order), the number of wave items, and k1_grid_ok (1: every
+ * item has a taker -- the check Engine::seg_prologue fails a segment on).
+ * items (may be NULL; 3 uint64 per item, items_cap items, which must hold
+ * them all) receives each item's kU, first chunk c0 and level end rend: lane
+ * j walks the chunks [c0 + j * kU, min(c0 + (j + 1) * kU, rend)).  Tests only
+ * (tests/test_schedule_corpus.py). */
+int tsg_test_k1_schedule(uint64_t nchunks, uint32_t blocks, uint32_t rounds, int top8, uint64_t* levels,
+                         uint64_t* items, size_t items_cap);
+
 /* Test hook: the engine's next n segment runs fail before their first
  * launch (as a failed device allocation would), so a test can check that a
  * failed call leaves nothing behind on the engine's pooled lanes.  Never used

@@ -15,9 +15,15 @@ def where(c, f, start, chunk):
         return "start kFullScanStart"
     b = int(c.offsets[f]) + start
     return ("start %d = batch offset %d (mod chunk %d: %d, mod 64: %d, mod 4 chunks: %d, mod 8 chunks: %d, "
-            "mod 64 KiB: %d; %d bytes before the file's end; batch of %d bytes)"
+            "mod 64 KiB: %d; %d bytes before the file's end; batch of %d bytes)%s"
             % (start, b, chunk, b % chunk, b % 64, b % (4 * chunk), b % (8 * chunk), b % EC.BLOCK,
-               int(c.offsets[f + 1]) - b, c.nbytes))
+               int(c.offsets[f + 1]) - b, c.nbytes, located(c, b)))
+
+
+def located(c, b):
+    """The wave item, level and lane of a batch offset where the corpus knows
+    K1's schedule (tests/_schedule_corpus.py: note["locate"])."""
+    return "; " + c.note["locate"](b) if "locate" in c.note else ""
 
 
 def check(c, rule_ids, got, info, want, winfo, expect_chunk=None):
@@ -44,10 +50,12 @@ def check(c, rule_ids, got, info, want, winfo, expect_chunk=None):
     total = int(offsets[-1])
     nl = info["chunk_newlines"]
     assert len(nl) == -(-total // chunk), (c.name, len(nl), total, chunk)
-    ref = np.add.reduceat((data[:total] == 10).astype(np.int64), np.arange(0, total, chunk)) if total else np.zeros(0)
+    # (summed as int64 without an int64 copy of the batch: the schedule corpora are hundreds of MB)
+    ref = np.add.reduceat(data[:total] == 10, np.arange(0, total, chunk), dtype=np.int64) if total else np.zeros(0)
     bad = np.nonzero(nl.astype(np.int64) != ref)[0]
-    assert len(bad) == 0, ("%s: newline count of chunk %d (batch offset %d, chunk %d): GPU %d, batch %d; %d chunks differ"
-                           % (c.name, bad[0], bad[0] * chunk, chunk, nl[bad[0]], ref[bad[0]], len(bad)))
+    assert len(bad) == 0, ("%s: newline count of chunk %d (batch offset %d, chunk %d): GPU %d, batch %d; %d chunks differ%s"
+                           % (c.name, bad[0], bad[0] * chunk, chunk, nl[bad[0]], ref[bad[0]], len(bad),
+                              located(c, int(bad[0]) * chunk)))
     # ---- file flags: bit 0 (engine.h kFileFoldSpecial) is the only bit K1 sets
     flags = info["flags"]
     assert len(flags) == len(c.args)

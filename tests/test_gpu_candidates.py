@@ -36,6 +36,10 @@ SETTINGS = {
     "chunk512": {"TSG_K1_CHUNK": "512"},
     "chunk2048": {"TSG_K1_CHUNK": "2048"},
     "top8": {"TSG_K1_TOP8": "2", "TSG_K1_TAIL_ROUNDS": "0"},
+    # ... at the chunk the product runs that level with (launches of >= 2 GiB),
+    # and at 4096 B: a 2 MiB wave item, the hit record's offset limit
+    "top8_1024": {"TSG_K1_TOP8": "2", "TSG_K1_TAIL_ROUNDS": "0", "TSG_K1_CHUNK": "1024"},
+    "top8_4096": {"TSG_K1_TOP8": "2", "TSG_K1_TAIL_ROUNDS": "0", "TSG_K1_CHUNK": "4096"},
 }
 
 _RULESETS = {}      # ruleset -> (model scanner, rule table, probes)

@@ -153,9 +153,10 @@ def test_k1_variants_agree_gpu(monkeypatch, abl, chunk):
 def test_k1_top8_schedule_gpu(monkeypatch, chunk, rounds):
     # the kU = 8 bulk level (TSG_K1_TOP8, launches of >= 2 GiB) forced onto a
     # 24 MB batch: with no tail rounds every wave item is 64 lanes x 8 chunks
-    # (4096-B chunks: a 2 MiB item, the hit record's offset limit; the levels
-    # below it run in every launch of >= 2 GiB, bench.py's resident leg and
-    # same_findings)
+    # (4096-B chunks: a 2 MiB item, the hit record's offset limit), all in the
+    # first static round.  Resident pieces never run this level; the levels
+    # below it, their boundaries and the per-XCD counters are compared with
+    # the CPU model item by item in tests/test_gpu_k1_schedule.py
     c = synth.generate(24_000_000, seed=31, sizes="loguniform", plant_rate=3e-3)
     args = [S.ScanArgs(c.paths[i], c.file(i)) for i in range(len(c.paths))]
     want = _oracle_all("variants", args)

@@ -154,6 +154,8 @@ SIGNATURES = [
     ("tsg_test_plan_wire_strips", ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                                   ctypes.POINTER(ctypes.c_uint32)]),
+    ("tsg_test_k1_schedule", ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
     ("tsg_test_engine_footprint", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
                                                   ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
     ("tsg_test_keep_raw", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),

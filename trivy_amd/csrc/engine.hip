@@ -1426,6 +1426,7 @@ uint32_t k1_chunk_for(uint64_t bytes, uint32_t lanes, int top8, bool resident) {
 
 }  // namespace tsg
 #include "confirm.h"   // (this file's include block belongs to K1's build hash)
+#include "k1_schedule.h"   // the host's restatement of K1's item schedule (the guard in seg_prologue)
 namespace tsg {
 
 namespace {
@@ -2348,6 +2349,17 @@ bool Engine::seg_prologue(SegRun& r, int attempt, std::string* err) {
   // one resident workgroup per CU (the LDS table takes most of the CU's
   // 160 KiB): a grid of at most one workgroup per CU, waves take items
   r.blocks = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(want_blocks, static_cast<uint32_t>(r.dt.sms))));
+  // every wave item needs a taker (k1_schedule.h): the per-XCD counters serve
+  // only a grid of 8 or more workgroups, so a smaller one -- a device with
+  // fewer than 8 CUs -- must fit its items into the static round.  (The
+  // one-counter measurement builds deal every item from one counter.)
+  static_assert(kK1Threads / 64 == kK1WavesPerBlock, "k1_schedule.h states the workgroup's waves");
+  const uint64_t waves = static_cast<uint64_t>(r.blocks) * kK1WavesPerBlock;
+  if (!(k1_abl_ & (kAblOneCounter | kAblAtomicFirst)) &&
+      !k1_grid_ok(r.blocks, k1_levels(r.nchunks, waves, k1_tail_rounds_, r.top8).nitems, waves)) {
+    *err = "K1 grid of fewer than 8 workgroups cannot take all its wave items";
+    return false;
+  }
   r.st->k1_blocks = r.blocks;
   r.st->k1_threads = kK1Threads;
   r.st->table_in_lds = 1;

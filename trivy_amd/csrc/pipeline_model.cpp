@@ -1,5 +1,6 @@
 // CPU models of Engine::scan's host logic for tests without a GPU: the
-// segment planner (segments.h, tsg_test_plan_segments, at the end) and the
+// segment planner (segments.h, tsg_test_plan_segments, at the end), K1's item
+// schedule (k1_schedule.h, tsg_test_k1_schedule, after it) and the
 // multi-device segment pipeline (pipeline.h) for
 // tests and sanitizer runs without a GPU: `ndevices` simulated device drivers
 // pull segments from the shared counter, each holding a lane from its
@@ -21,6 +22,7 @@
 #include <thread>
 #include <vector>
 
+#include "k1_schedule.h"
 #include "pipeline.h"
 #include "segments.h"
 #include "trivy_secret.h"
@@ -205,4 +207,24 @@ extern "C" int tsg_test_plan_wire_strips(uint64_t segment_bytes, uint64_t strip,
   } catch (const std::bad_alloc&) {
     return capi_fail(TSG_ERR_INTERNAL, "out of memory");
   }
+}
+
+extern "C" int tsg_test_k1_schedule(uint64_t nchunks, uint32_t blocks, uint32_t rounds, int top8, uint64_t* levels,
+                                    uint64_t* items, size_t items_cap) {
+  using namespace tsg;
+  if (!levels || blocks == 0 || rounds > 255 || (items_cap && !items)) return capi_fail(TSG_ERR_INVALID, "bad argument");
+  const uint64_t W = static_cast<uint64_t>(blocks) * kK1WavesPerBlock;
+  const K1Levels lv = k1_levels(nchunks, W, rounds, top8 != 0);
+  for (int l = 0; l < 4; ++l) levels[3 - l] = lv.chunks[l];        // n8, n4, n2, n1
+  levels[4] = lv.nitems;
+  levels[5] = k1_grid_ok(blocks, lv.nitems, W) ? 1 : 0;
+  if (!items) return TSG_OK;
+  if (lv.nitems > items_cap) return capi_fail(TSG_ERR_INVALID, "more items than items_cap");
+  for (uint64_t i = 0; i < lv.nitems; ++i) {
+    const K1Item it = k1_item(lv, i);
+    items[3 * i] = it.kU;
+    items[3 * i + 1] = it.c0;
+    items[3 * i + 2] = it.rend;
+  }
+  return TSG_OK;
 }

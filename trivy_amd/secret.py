@@ -1315,6 +1315,26 @@ def plan_segments(offsets, resident=False, base=0, with_paths=True, **policy):
     return segs
 
 
+def k1_schedule(nchunks, blocks, rounds=1, top8=False, with_items=True):
+    """K1's item schedule as the host restates it (tsg_test_k1_schedule,
+    csrc/k1_schedule.h) for nchunks chunks on `blocks` workgroups: {"n8", "n4",
+    "n2", "n1": chunks per level, "nitems", "grid_ok", "W": blocks * 16, and
+    with_items "kU", "c0", "rend": np.uint64 arrays, one entry per item}.
+    Tests only."""
+    L = _lib.lib()
+    lv = np.zeros(6, np.uint64)
+    _lib.check(L.tsg_test_k1_schedule(nchunks, blocks, rounds, int(top8), lv.ctypes.data, None, 0))
+    out = {"n8": int(lv[0]), "n4": int(lv[1]), "n2": int(lv[2]), "n1": int(lv[3]), "nitems": int(lv[4]),
+           "grid_ok": bool(lv[5]), "W": 16 * blocks}
+    if with_items:
+        items = np.zeros((max(out["nitems"], 1), 3), np.uint64)
+        _lib.check(L.tsg_test_k1_schedule(nchunks, blocks, rounds, int(top8), lv.ctypes.data, items.ctypes.data,
+                                          len(items)))
+        items = items[:out["nitems"]].astype(np.int64)
+        out["kU"], out["c0"], out["rend"] = items[:, 0].copy(), items[:, 1].copy(), items[:, 2].copy()
+    return out
+
+
 def prefilter_report(scanner):
     buf = ctypes.c_void_p()
     _lib.check(_lib.lib().tsg_prefilter_report(scanner._rs, ctypes.byref(buf)))
