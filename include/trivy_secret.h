@@ -418,6 +418,57 @@ const char* tsg_inflate_status_text(int32_t status);
  * mod 2^32 of that member alone -- a hint for the slot's size, no more.
  * TSG_ERR_INVALID when gz does not start like a gzip stream. */
 int tsg_gzip_size_hint(const uint8_t* gz, size_t len, uint64_t* isize);
+/* ---- zstd layers decoded on the GPU ----
+ * layer.Uncompressed() (pkg/fanal/artifact/image/image.go:464-492; at
+ * go-containerregistry v0.20.3) peeks a layer's first bytes and unwraps gzip
+ * (1f 8b), zstd (28 b5 2f fd; klauspost/compress) or nothing: layers of type
+ * application/vnd.oci.image.layer.v1.tar+zstd are what current buildkit and
+ * containerd write when asked.  tsg_inflate_zstd_device is that step for a
+ * batch of zstd streams that lies in HBM, beside tsg_inflate_gzip_device at
+ * the head of the same chain; its arguments, its buffers' rules (alignment, no
+ * overlap, the 16-byte-load convention for d_z, nothing outside a slot written
+ * and nothing past a stream's end read into its result) and its return values
+ * are that call's.  RFC 8878: concatenated and skippable frames; raw, RLE and
+ * compressed blocks; raw, RLE, Huffman (one or four streams) and treeless
+ * literals; predefined, RLE, FSE and repeat sequence tables; the content
+ * checksum (XXH64) and Frame_Content_Size are checked.  Dictionaries are not
+ * supported.  One wavefront decodes one stream; a match older than the wave's
+ * 32 KiB of LDS history is read back from the slot in HBM.  status[i]:
+ *   TSG_ZSTD_OK
+ *   TSG_ZSTD_HEADER     bad magic, a reserved bit, an impossible window
+ *   TSG_ZSTD_CORRUPT
+ *   TSG_ZSTD_EOF        the stream ends inside a frame
+ *   TSG_ZSTD_CHECKSUM
+ *   TSG_ZSTD_DICT       the frame names a dictionary
+ *   TSG_ZSTD_DST_FULL   the output did not fit the slot: call again with a larger one
+ * -- the first error in stream order; the statuses and their texts are this
+ * library's own (no Go decoder was run against them).  Where a stream both
+ * overflows its slot and is malformed further on, the slot comes first. */
+enum {
+  TSG_ZSTD_OK = 0,
+  TSG_ZSTD_HEADER = 1,
+  TSG_ZSTD_CORRUPT = 2,
+  TSG_ZSTD_EOF = 3,
+  TSG_ZSTD_CHECKSUM = 4,
+  TSG_ZSTD_DICT = 5,
+  TSG_ZSTD_DST_FULL = 6
+};
+int tsg_inflate_zstd_device(tsg_engine* e, const void* d_z, const uint64_t* z_offsets, uint32_t nstreams,
+                            void* d_dst, const uint64_t* dst_offsets, uint64_t* out_lens, int32_t* status, double* ms);
+/* The text of a status ("" for TSG_ZSTD_OK and TSG_ZSTD_DST_FULL) */
+const char* tsg_zstd_status_text(int32_t status);
+/* An upper bound of the decoded size of a zstd stream in host memory, from its
+ * frame and block headers alone: the sum of Frame_Content_Size where every
+ * frame has one (*exact = 1), else a raw or RLE block counts its size and a
+ * compressed block Block_Maximum_Size.  An RLE block expands 128 KiB from
+ * four bytes, so no multiple of the compressed size is a bound; this is.
+ * TSG_ERR_INVALID when the walk meets a malformed or truncated header; *bound
+ * then covers what precedes it. */
+int tsg_zstd_size_bound(const uint8_t* z, size_t len, uint64_t* bound, int* exact);
+/* How a layer blob is compressed, by its first bytes as go-containerregistry's
+ * peek decides: 1f 8b gzip, 28 b5 2f fd zstd, anything else a plain tar. */
+enum { TSG_LAYER_NONE = 0, TSG_LAYER_GZIP = 1, TSG_LAYER_ZSTD = 2 };
+int tsg_layer_compression(const uint8_t* blob, size_t len);
 /* `trivy fs` over a directory tree on disk: walker.FS.Walk (pkg/fanal/walker/
  * fs.go:25-97; filepath.WalkDir order, symlinks not followed, defaultSkipDirs
  * **\/.git proc sys dev, permission errors ignored), AnalyzeFile's gate before

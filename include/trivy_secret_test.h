@@ -401,6 +401,24 @@ int tsg_test_crc32_slices(const uint8_t* data, uint64_t len, uint32_t* crc, uint
  * members it found and the slices it summed.  Any pointer may be NULL. */
 int tsg_test_inflate_last_stats(double* inflate_ms, double* crc_ms, uint64_t* members, uint64_t* slices);
 
+/* The CPU model of tsg_inflate_zstd_device (zstdec.h's zstd_model): the same
+ * arguments with z and dst in host memory and e unused (may be NULL);
+ * status[] and out_lens[] are what the device call gives.  Nothing outside a
+ * stream's slot is written. */
+int tsg_test_zstd_model(tsg_engine* e, const void* z, const uint64_t* z_offsets, uint32_t nstreams, void* dst,
+                        const uint64_t* dst_offsets, uint64_t* out_lens, int32_t* status, double* ms);
+/* What one stream exercises, counted by the model while it decodes it into a
+ * slot of cap bytes of its own: counters[0, ncounters) in the order of
+ * zstdec.h's kEv* (tools/gen_zstd_corpus.py holds the names); *status = the
+ * stream's status. */
+int tsg_test_zstd_trace(const uint8_t* z, size_t len, uint64_t cap, uint64_t* counters, uint32_t ncounters, int32_t* status);
+/* The kernel times of the calling thread's last tsg_inflate_zstd_device call
+ * (tools/zstd_probe.py): the decode and the hash kernel in ms, the frames and
+ * blocks it decoded.  Any pointer may be NULL. */
+int tsg_test_zstd_last_stats(double* decode_ms, double* hash_ms, uint64_t* frames, uint64_t* blocks);
+/* XXH64 (seed 0) of data[0, len) as the checksum pass computes it */
+int tsg_test_xxh64(const uint8_t* data, uint64_t len, uint64_t* hash);
+
 #ifdef __cplusplus
 }
 #endif

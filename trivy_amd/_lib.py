@@ -267,6 +267,29 @@ SIGNATURES += [
 # per-stream status of tsg_inflate_gzip_device
 INFLATE_OK, INFLATE_HEADER, INFLATE_CORRUPT, INFLATE_EOF, INFLATE_CHECKSUM, INFLATE_DST_FULL = range(6)
 
+SIGNATURES += [
+    ("tsg_inflate_zstd_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.POINTER(ctypes.c_double)]),
+    ("tsg_zstd_status_text", ctypes.c_char_p, [ctypes.c_int32]),
+    ("tsg_zstd_size_bound", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64),
+                                           ctypes.POINTER(ctypes.c_int)]),
+    ("tsg_layer_compression", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t]),
+    ("tsg_test_zstd_model", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.POINTER(ctypes.c_double)]),
+    ("tsg_test_zstd_trace", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p,
+                                           ctypes.c_uint32, ctypes.POINTER(ctypes.c_int32)]),
+    ("tsg_test_zstd_last_stats", ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                                ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    ("tsg_test_xxh64", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+]
+
+# per-stream status of tsg_inflate_zstd_device
+ZSTD_OK, ZSTD_HEADER, ZSTD_CORRUPT, ZSTD_EOF, ZSTD_CHECKSUM, ZSTD_DICT, ZSTD_DST_FULL = range(7)
+# tsg_layer_compression
+LAYER_NONE, LAYER_GZIP, LAYER_ZSTD = range(3)
+
 # tsg_read_fn: int64_t (*)(void* user, uint8_t* buf, size_t cap)
 READ_FN = ctypes.CFUNCTYPE(ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
 

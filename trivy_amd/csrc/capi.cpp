@@ -22,6 +22,7 @@
 #include "gosort.h"
 #include "guard.h"
 #include "inflate_dev.h"
+#include "zstdec_dev.h"
 #include "feed.h"
 #include "tar.h"
 #include "tarscan.h"
@@ -68,6 +69,7 @@ struct tsg_ruleset {
 struct tsg_engine {
   std::unique_ptr<Engine> eng;   // reentrant: every call takes its own lanes (streams + buffers)
   std::string report;
+  ZstdScratch zstd;              // tsg_inflate_zstd_device's literal scratch
 };
 
 struct tsg_prepared {
@@ -1834,6 +1836,95 @@ int tsg_test_inflate_last_stats(double* inflate_ms, double* crc_ms, uint64_t* me
   if (members) *members = g_inflate_stats.members;
   if (slices) *slices = g_inflate_stats.slices;
   return TSG_OK;
+}
+
+static_assert(TSG_ZSTD_OK == kZsOk && TSG_ZSTD_HEADER == kZsHeader && TSG_ZSTD_CORRUPT == kZsCorrupt && TSG_ZSTD_EOF == kZsEof &&
+                  TSG_ZSTD_CHECKSUM == kZsChecksum && TSG_ZSTD_DICT == kZsDict && TSG_ZSTD_DST_FULL == kZsDstFull,
+              "zstdec.h and trivy_secret.h number the statuses alike");
+static_assert(TSG_LAYER_NONE == kLayerNone && TSG_LAYER_GZIP == kLayerGzip && TSG_LAYER_ZSTD == kLayerZstd,
+              "zstdec.h and trivy_secret.h number the layer kinds alike");
+
+namespace {
+thread_local ZstdStats g_zstd_stats;
+// TSG_OK, or TSG_ERR_INVALID naming the first stream that is not TSG_ZSTD_OK
+int zstd_verdict(const int32_t* status, uint32_t nstreams) {
+  for (uint32_t i = 0; i < nstreams; ++i) {
+    if (status[i] == kZsOk) continue;
+    const char* text = status[i] == kZsDstFull ? "the output does not fit its slot" : zstd_status_text(status[i]);
+    return fail(TSG_ERR_INVALID, "zstd stream " + std::to_string(i) + ": " + text);
+  }
+  return TSG_OK;
+}
+}  // namespace
+
+int tsg_inflate_zstd_device(tsg_engine* e, const void* d_z, const uint64_t* z_offsets, uint32_t nstreams,
+                            void* d_dst, const uint64_t* dst_offsets, uint64_t* out_lens, int32_t* status, double* ms) {
+  TSG_API_TRY
+  if (!e || (nstreams && (!z_offsets || !dst_offsets || !out_lens || !status))) return fail(TSG_ERR_INVALID, "NULL argument");
+  if (ms) *ms = 0;
+  std::string err;
+  ZstdStats st;
+  if (!inflate_zstd_device(&e->zstd, d_z, z_offsets, nstreams, d_dst, dst_offsets, out_lens, status, &st, &err))
+    return fail(err.find("zstd:") == 0 ? TSG_ERR_INVALID : TSG_ERR_HIP, err);
+  g_zstd_stats = st;
+  if (ms) *ms = st.decode_ms + st.hash_ms;
+  return zstd_verdict(status, nstreams);
+  TSG_API_CATCH
+}
+
+const char* tsg_zstd_status_text(int32_t status) { return zstd_status_text(status); }
+
+int tsg_zstd_size_bound(const uint8_t* z, size_t len, uint64_t* bound, int* exact) {
+  TSG_API_TRY
+  if ((len && !z) || !bound || !exact) return fail(TSG_ERR_INVALID, "NULL argument");
+  if (!zstd_size_bound(z, len, bound, exact)) return fail(TSG_ERR_INVALID, "zstd: malformed or truncated frame or block header");
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_layer_compression(const uint8_t* blob, size_t len) { return blob ? layer_compression(blob, len) : TSG_LAYER_NONE; }
+
+int tsg_test_zstd_model(tsg_engine*, const void* z, const uint64_t* z_offsets, uint32_t nstreams, void* dst,
+                        const uint64_t* dst_offsets, uint64_t* out_lens, int32_t* status, double* ms) {
+  TSG_API_TRY
+  if (nstreams && (!z_offsets || !dst_offsets || !out_lens || !status)) return fail(TSG_ERR_INVALID, "NULL argument");
+  if (ms) *ms = 0;
+  for (uint32_t i = 0; i < nstreams; ++i) {
+    if (z_offsets[i] > z_offsets[i + 1] || dst_offsets[i] > dst_offsets[i + 1])
+      return fail(TSG_ERR_INVALID, "zstd: offsets must not decrease");
+    const uint8_t* src = static_cast<const uint8_t*>(z) + z_offsets[i];
+    status[i] = zstd_model([src](uint64_t k) { return static_cast<uint32_t>(src[k]); }, z_offsets[i + 1] - z_offsets[i],
+                           static_cast<uint8_t*>(dst) + dst_offsets[i], dst_offsets[i + 1] - dst_offsets[i], &out_lens[i]);
+  }
+  return zstd_verdict(status, nstreams);
+  TSG_API_CATCH
+}
+
+int tsg_test_zstd_trace(const uint8_t* z, size_t len, uint64_t cap, uint64_t* counters, uint32_t ncounters, int32_t* status) {
+  TSG_API_TRY
+  if ((len && !z) || !counters || !status) return fail(TSG_ERR_INVALID, "NULL argument");
+  std::vector<uint8_t> dst(cap + 1);
+  uint64_t ev[kEvCount] = {0}, out_len = 0;
+  *status = zstd_model([z](uint64_t k) { return static_cast<uint32_t>(z[k]); }, len, dst.data(), cap, &out_len, ev);
+  for (uint32_t k = 0; k < ncounters; ++k) counters[k] = k < kEvCount ? ev[k] : 0;
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_test_zstd_last_stats(double* decode_ms, double* hash_ms, uint64_t* frames, uint64_t* blocks) {
+  if (decode_ms) *decode_ms = g_zstd_stats.decode_ms;
+  if (hash_ms) *hash_ms = g_zstd_stats.hash_ms;
+  if (frames) *frames = g_zstd_stats.frames;
+  if (blocks) *blocks = g_zstd_stats.blocks;
+  return TSG_OK;
+}
+
+int tsg_test_xxh64(const uint8_t* data, uint64_t len, uint64_t* hash) {
+  TSG_API_TRY
+  if ((len && !data) || !hash) return fail(TSG_ERR_INVALID, "NULL argument");
+  *hash = zs_xxh64(ZsByteLd{data}, len);
+  return TSG_OK;
+  TSG_API_CATCH
 }
 
 int tsg_prepare_fs_tree(const tsg_ruleset* rs, const char* root, const tsg_feed_opts* opts, tsg_prepared** out) {

@@ -394,45 +394,205 @@ class Scanner:
         raises WalkError as PrepareLayerTarDevice does.  with_stats appends
         {"gz_bytes", "tar_bytes", "inflate_ms", "inflate_rounds"} to the list's
         tuple: (layers, stats)."""
+        views = self._blob_views(blobs)
+        opts = dict(skip_files=skip_files, skip_dirs=skip_dirs, file_patterns=file_patterns, config_path=config_path)
+        slots, st = self._gzip_layer_slots(views, list(range(len(views))))
+        layers = [self._scan_layer_slot(d_tar, k, opts, contents) for d_tar, k in slots]
+        if with_stats:
+            return layers, {"gz_bytes": st["gz_bytes"], "tar_bytes": sum(k for _, k in slots), "inflate_ms": st["ms"],
+                            "inflate_rounds": st["rounds"]}
+        return layers
+
+    # ---- what ScanLayersGzipDevice and ScanLayersCompressedDevice share ----
+    @staticmethod
+    def _blob_views(blobs):
+        import torch
+        return [b.numpy() if isinstance(b, torch.Tensor) else np.frombuffer(b, dtype=np.uint8) for b in blobs]
+
+    def _upload_blobs(self, views, idx, align=1):
+        """views[i] for i in idx, each starting at a multiple of align, through one pinned buffer in one copy:
+        (device tensor with 16 zero bytes behind the last blob, offsets of len(idx) + 1)"""
+        import torch
+        off = np.zeros(len(idx) + 1, np.uint64)
+        if idx:
+            np.cumsum([(len(views[i]) + align - 1) // align * align for i in idx], out=off[1:])
+        dev = torch.device("cuda", 0 if self._device == "all" else int(self._device))
+        host = torch.empty(int(off[-1]) + 16, dtype=torch.uint8).pin_memory()
+        hv = host.numpy()
+        for k, i in enumerate(idx):
+            a = int(off[k])
+            hv[a:a + len(views[i])] = views[i]
+            hv[a + len(views[i]):int(off[k + 1])] = 0
+        hv[int(off[-1]):] = 0
+        return host.to(dev, non_blocking=True), off
+
+    def _gzip_layer_slots(self, views, idx):
+        """The gzip blobs views[i], i in idx: one upload, one InflateGzipDevice.  ([(slot tensor, tar length)] in
+        idx's order, {"gz_bytes", "ms", "rounds"}); a stream that fails raises WalkError with its index i."""
+        L = _lib.lib()
+        hints = np.zeros(len(idx), np.int64)
+        for k, i in enumerate(idx):
+            h = ctypes.c_uint64()
+            if len(views[i]) and L.tsg_gzip_size_hint(views[i].ctypes.data, len(views[i]), ctypes.byref(h)) == 0:
+                hints[k] = h.value
+        d_gz, go = self._upload_blobs(views, idx)   # the one upload
+        dst, do, out_lens, status, ist = self.InflateGzipDevice(d_gz, go, hints=hints, with_stats=True)
+        for k, i in enumerate(idx):
+            if status[k] != _lib.INFLATE_OK:
+                text = L.tsg_inflate_status_text(int(status[k])).decode() or "the inflated layer does not fit its slot"
+                raise WalkError("layer %d: %s" % (i, text))
+        slots = [(dst[int(do[k]):int(do[k + 1])], int(out_lens[k])) for k in range(len(idx))]
+        return slots, {"gz_bytes": int(go[-1]), "ms": ist["ms"], "rounds": ist["rounds"]}
+
+    def _scan_layer_slot(self, d_tar, k, opts, contents):
+        """PrepareLayerTarDevice -> ScanBatchDevice on a tar of k bytes in HBM: (ScanArgs list, walk dict, [types.Secret])"""
+        p_dst, offs, scan_paths, binf, walk, _ms = self.PrepareLayerTarDevice(d_tar, k, **opts)
+        secrets = self.ScanBatchDevice(p_dst, offs, scan_paths, binf)
+        data = p_dst[:int(offs[-1])].cpu().numpy().tobytes() if contents and len(scan_paths) else None
+        args = [ScanArgs(p, data[int(offs[j]):int(offs[j + 1])] if data is not None else (b"" if contents else None),
+                         bool(binf[j])) for j, p in enumerate(scan_paths)]
+        return args, walk, secrets
+
+    def InflateZstdDevice(self, d_z, z_offsets, caps=None, bounds=None, max_regrow=9, with_stats=False):
+        """A batch of zstd streams that lies in HBM, decoded there
+        (tsg_inflate_zstd_device): what layer.Uncompressed() does to a layer
+        that starts 28 b5 2f fd, for all such layers at once, one wavefront per
+        stream.
+
+        d_z, z_offsets: as InflateGzipDevice's d_gz, gz_offsets.  caps: each
+        stream's slot size; default bounds + 64 rounded up to 16 bytes, where
+        bounds is tsg_zstd_size_bound of every stream (the caller's, taken
+        from the blobs before the upload; else the streams are read back from
+        d_z once to walk their headers).  The decoder lets no block regenerate
+        more than Block_Maximum_Size, so the bound holds for every stream the
+        walk accepts, and only a caller's own small caps (or a stream whose
+        headers are malformed) end in TSG_ZSTD_DST_FULL; such a stream is run
+        again in a slot twice as large, at most max_regrow times; only those
+        streams run again, the others' outputs are copied on the device.
+
+        Returns (d_dst, dst_offsets, out_lens, status) as InflateGzipDevice
+        does, status[i] a TSG_ZSTD_* value (_lib.ZSTD_OK ...; the text:
+        tsg_zstd_status_text).  with_stats appends {"ms", "rounds"}."""
         import torch
         L = _lib.lib()
-        views = [b.numpy() if isinstance(b, torch.Tensor) else np.frombuffer(b, dtype=np.uint8) for b in blobs]
-        n = len(views)
-        go = np.zeros(n + 1, np.uint64)
-        if n:
-            np.cumsum([len(v) for v in views], out=go[1:])
-        hints = np.zeros(n, np.int64)
-        for i, v in enumerate(views):
-            h = ctypes.c_uint64()
-            if len(v) and L.tsg_gzip_size_hint(v.ctypes.data, len(v), ctypes.byref(h)) == 0:
-                hints[i] = h.value
-        dev = torch.device("cuda", 0 if self._device == "all" else int(self._device))
-        host = torch.empty(int(go[-1]) + 16, dtype=torch.uint8).pin_memory()
-        hv = host.numpy()
-        for i, v in enumerate(views):
-            hv[int(go[i]):int(go[i + 1])] = v
-        hv[int(go[-1]):] = 0
-        d_gz = host.to(dev, non_blocking=True)   # the one upload
-        dst, do, out_lens, status, ist = self.InflateGzipDevice(d_gz, go, hints=hints, with_stats=True)
-        for i in range(n):
-            if status[i] != _lib.INFLATE_OK:
-                text = L.tsg_inflate_status_text(int(status[i])).decode() or "the inflated layer does not fit its slot"
-                raise WalkError("layer %d: %s" % (i, text))
-        layers = []
-        for i in range(n):
-            k = int(out_lens[i])
-            d_tar = dst[int(do[i]):int(do[i + 1])]
-            p_dst, offs, scan_paths, binf, walk, _ms = self.PrepareLayerTarDevice(
-                d_tar, k, skip_files=skip_files, skip_dirs=skip_dirs, file_patterns=file_patterns, config_path=config_path)
-            secrets = self.ScanBatchDevice(p_dst, offs, scan_paths, binf)
-            data = p_dst[:int(offs[-1])].cpu().numpy().tobytes() if contents and len(scan_paths) else None
-            args = [ScanArgs(p, data[int(offs[j]):int(offs[j + 1])] if data is not None else (b"" if contents else None),
-                             bool(binf[j])) for j, p in enumerate(scan_paths)]
-            layers.append((args, walk, secrets))
-        if with_stats:
-            return layers, {"gz_bytes": int(go[-1]), "tar_bytes": int(out_lens.sum()), "inflate_ms": ist["ms"],
-                            "inflate_rounds": ist["rounds"]}
-        return layers
+        zo = np.ascontiguousarray(z_offsets, dtype=np.uint64)
+        n = len(zo) - 1
+        if n < 0:
+            raise ValueError("z_offsets must hold at least one entry")
+        if d_z.dtype != torch.uint8 or not d_z.is_cuda or not d_z.is_contiguous() or d_z.data_ptr() & 15:
+            raise ValueError("d_z must be a contiguous, 16-byte aligned uint8 device tensor")
+        if n and d_z.numel() < int(zo[-1]):
+            raise ValueError("d_z is shorter than the batch")
+        if caps is None:
+            if bounds is None:
+                host = d_z[:int(zo[-1])].cpu().numpy() if n else np.zeros(0, np.uint8)
+                bounds = [self.ZstdSizeBound(host[int(zo[i]):int(zo[i + 1])])[0] for i in range(n)]
+            caps = np.asarray(bounds, np.int64) + 64
+        caps = (np.asarray(caps, np.int64) + 15) & ~15 if n else np.zeros(0, np.int64)
+        if len(caps) != n:
+            raise ValueError("caps must hold one entry per stream")
+        status = np.full(n, _lib.ZSTD_DST_FULL, np.int32)
+        out_lens = np.zeros(n, np.uint64)
+        dst, do, ms, rounds = None, None, 0.0, 0
+        torch.cuda.current_stream(d_z.device).synchronize()      # the call runs on its own stream
+        while True:
+            new_do = np.zeros(n + 1, np.uint64)
+            np.cumsum(caps, out=new_do[1:])
+            new = torch.empty(max(int(new_do[-1]), 16) + 16, dtype=torch.uint8, device=d_z.device)
+            todo = np.flatnonzero(status == _lib.ZSTD_DST_FULL)
+            if dst is not None:                  # what is done moves over on the device
+                for i in np.flatnonzero(status != _lib.ZSTD_DST_FULL):
+                    k = int(out_lens[i])
+                    new[int(new_do[i]):int(new_do[i]) + k] = dst[int(do[i]):int(do[i]) + k]
+                torch.cuda.current_stream(d_z.device).synchronize()
+            dst, do = new, new_do
+            runs = np.split(todo, np.flatnonzero(np.diff(todo) != 1) + 1) if len(todo) else []
+            for run in runs:                     # adjacent streams go in one launch
+                a, b = int(run[0]), int(run[-1]) + 1
+                g, d = np.ascontiguousarray(zo[a:b + 1]), np.ascontiguousarray(do[a:b + 1])
+                t = ctypes.c_double()
+                rc = L.tsg_inflate_zstd_device(self.engine(), ctypes.c_void_p(d_z.data_ptr()), g.ctypes.data, b - a,
+                                               ctypes.c_void_p(dst.data_ptr()), d.ctypes.data,
+                                               out_lens[a:b].ctypes.data, status[a:b].ctypes.data, ctypes.byref(t))
+                if rc != 0 and not L.tsg_last_error().startswith(b"zstd stream "):
+                    _lib.check(rc)               # the call itself failed, not a stream
+                ms += t.value
+            full = status == _lib.ZSTD_DST_FULL
+            if not full.any() or rounds >= max_regrow:
+                break
+            rounds += 1
+            caps = np.where(full, caps * 2, caps)
+        out = (dst, do, out_lens, status)
+        return out + ({"ms": ms, "rounds": rounds},) if with_stats else out
+
+    @staticmethod
+    def ZstdSizeBound(blob):
+        """tsg_zstd_size_bound of a zstd stream in host memory: (bound, exact,
+        clean) -- clean is False when the walk met a malformed or truncated
+        header; the bound then covers what precedes it."""
+        L = _lib.lib()
+        v = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8))
+        bound, exact = ctypes.c_uint64(), ctypes.c_int()
+        rc = L.tsg_zstd_size_bound(v.ctypes.data if len(v) else None, len(v), ctypes.byref(bound), ctypes.byref(exact))
+        return int(bound.value), bool(exact.value), rc == 0
+
+    @staticmethod
+    def LayerCompression(blob):
+        """tsg_layer_compression: _lib.LAYER_NONE / LAYER_GZIP / LAYER_ZSTD by the blob's first bytes."""
+        v = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8)[:4])
+        return int(_lib.lib().tsg_layer_compression(v.ctypes.data if len(v) else None, len(v)))
+
+    def ScanLayersCompressedDevice(self, blobs, skip_files=(), skip_dirs=(), file_patterns=(), config_path="",
+                                   with_stats=False, contents=False):
+        """ScanLayersGzipDevice for layers as layer.Uncompressed() takes them:
+        each blob is a gzip stream, a zstd stream or a plain tar, told apart by
+        its first bytes (tsg_layer_compression) as go-containerregistry's peek
+        does.
+
+            gzip blobs: one upload -> InflateGzipDevice (one launch)
+            zstd blobs: one upload -> InflateZstdDevice (one launch)
+            plain tars: uploaded as they are
+            then per layer, in blob order: PrepareLayerTarDevice -> ScanBatchDevice
+
+        Arguments and the per-layer result are ScanLayersGzipDevice's.  A
+        stream that fails raises WalkError with its blob index and the status
+        text.  with_stats appends {"gz_bytes", "zstd_bytes", "plain_bytes",
+        "tar_bytes", "inflate_ms", "zstd_ms", "inflate_rounds"}."""
+        L = _lib.lib()
+        views = self._blob_views(blobs)
+        kinds = [int(L.tsg_layer_compression(v.ctypes.data, min(len(v), 4))) if len(v) else _lib.LAYER_NONE for v in views]
+        opts = dict(skip_files=skip_files, skip_dirs=skip_dirs, file_patterns=file_patterns, config_path=config_path)
+        slots = [None] * len(views)              # per blob: (device tensor that holds the tar, its length)
+        stats = {"gz_bytes": 0, "zstd_bytes": 0, "plain_bytes": 0, "tar_bytes": 0, "inflate_ms": 0.0, "zstd_ms": 0.0,
+                 "inflate_rounds": 0}
+        gz = [i for i, k in enumerate(kinds) if k == _lib.LAYER_GZIP]
+        zs = [i for i, k in enumerate(kinds) if k == _lib.LAYER_ZSTD]
+        plain = [i for i, k in enumerate(kinds) if k == _lib.LAYER_NONE]
+        if gz:
+            got, st = self._gzip_layer_slots(views, gz)
+            for i, slot in zip(gz, got):
+                slots[i] = slot
+            stats["gz_bytes"], stats["inflate_ms"] = st["gz_bytes"], st["ms"]
+            stats["inflate_rounds"] += st["rounds"]
+        if zs:
+            bounds = [self.ZstdSizeBound(views[i])[0] for i in zs]
+            d_z, zo = self._upload_blobs(views, zs)
+            dst, do, out_lens, status, ist = self.InflateZstdDevice(d_z, zo, bounds=bounds, with_stats=True)
+            for k, i in enumerate(zs):
+                if status[k] != _lib.ZSTD_OK:
+                    text = L.tsg_zstd_status_text(int(status[k])).decode() or "the decoded layer does not fit its slot"
+                    raise WalkError("layer %d: %s" % (i, text))
+                slots[i] = (dst[int(do[k]):int(do[k + 1])], int(out_lens[k]))
+            stats["zstd_bytes"], stats["zstd_ms"] = int(zo[-1]), ist["ms"]
+            stats["inflate_rounds"] += ist["rounds"]
+        if plain:                                # one upload for all of them, every tar 16-byte aligned
+            d_p, po = self._upload_blobs(views, plain, align=16)
+            for k, i in enumerate(plain):
+                slots[i] = (d_p[int(po[k]):int(po[k + 1]) + (16 if k == len(plain) - 1 else 0)], len(views[i]))
+                stats["plain_bytes"] += len(views[i])
+        layers = [self._scan_layer_slot(d_tar, k, opts, contents) for d_tar, k in slots]
+        stats["tar_bytes"] = sum(k for _, k in slots)
+        return (layers, stats) if with_stats else layers
 
     def ScanLayerGzipDevice(self, blob, **kw):
         """ScanLayersGzipDevice for one layer: (ScanArgs list, walk dict, [types.Secret])."""
