@@ -180,6 +180,34 @@ int tsg_scan_batch_resident(tsg_engine* e, const void* d_data, const uint8_t* h_
 int tsg_scan_batch_device(tsg_engine* e, const void* d_data, const uint64_t* offsets, uint32_t nfiles,
                           const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
                           tsg_result** out);
+/* The device-only scan gathering windows around candidates instead of whole
+ * files: for a batch of large files (logs, dumps, bundles) whose every file
+ * has a candidate, the whole batch would otherwise cross the link.  With a
+ * window set, a file whose candidates all belong to rules the confirmer
+ * decides from a candidate start alone contributes the K1 chunk holding its
+ * first byte and, per candidate start s, the chunks of [s - window_before,
+ * s + window_after) clipped to the file; chunks that touch form one run.
+ * Files stay whole when they are fold-special, when the rule set has a
+ * host-evaluated rule, when a candidate belongs to a presence rule, a
+ * host-gated keyword rule or an exclude block, when they are shorter than
+ * window_min_file, or when their windows take more than half of their chunks.
+ * The confirmer works on the runs and notes every read that would leave them
+ * on a side that is not the file's own start or end (a regex run that examined
+ * a byte at or past its run's end, a line search that met a run's edge, fewer
+ * than 4 bytes in front of a candidate); such a file's result is dropped, and
+ * at the end of the call those files are gathered whole in one more round and
+ * confirmed as tsg_scan_batch_device confirms.  The result is
+ * tsg_scan_batch_resident's, byte for byte, for every setting.  opts NULL, or
+ * both window sizes 0: tsg_scan_batch_device in every respect.  d_data must
+ * stay valid for the whole call. */
+typedef struct tsg_device_scan_opts {
+  uint32_t window_before;   /* bytes gathered in front of a candidate start; 0 with window_after 0: whole files */
+  uint32_t window_after;    /* bytes gathered from a candidate start on */
+  uint64_t window_min_file; /* files shorter than this are gathered whole */
+} tsg_device_scan_opts;
+int tsg_scan_batch_device_opts(tsg_engine* e, const void* d_data, const uint64_t* offsets, uint32_t nfiles,
+                               const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
+                               const tsg_device_scan_opts* opts, tsg_result** out);
 
 /* Host-feed ceiling: stream `bytes` of host memory (pinned for full rate) to
  * HBM through the engine's upload path in segments, with no kernels; *ms =
@@ -223,6 +251,13 @@ int tsg_result_stats(const tsg_result* r, tsg_stats* out);
  * launches repeated with a larger buffer.  Any pointer may be NULL. */
 int tsg_result_gather_stats(const tsg_result* r, uint64_t* files, uint64_t* bytes, uint64_t* runs, double* ms,
                             uint32_t* retries);
+/* ... of a tsg_scan_batch_device_opts result with windows (all 0 otherwise):
+ * files confirmed from windows, the runs and bytes of the windowed layouts
+ * (the whole files in them included), and the files and bytes of the fallback
+ * round.  tsg_result_gather_stats' bytes and runs hold both rounds: everything
+ * that crossed for the confirmer.  Any pointer may be NULL. */
+int tsg_result_gather_window_stats(const tsg_result* r, uint64_t* window_files, uint64_t* window_runs,
+                                   uint64_t* window_bytes, uint64_t* fallback_files, uint64_t* fallback_bytes);
 /* Frees a result; one of >= 4096 files + findings is handed to a background
    thread (its memory returns shortly after the call). */
 void tsg_result_free(tsg_result* r);

@@ -131,6 +131,54 @@ int tsg_scan_device_model_release(const tsg_ruleset* rs, const uint8_t* data, co
                                   const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
                                   uint32_t chunk, void (*release)(void* user), void* user, tsg_result** out);
 
+/* The device-only scan with windows (tsg_scan_batch_device_opts), on the CPU.
+ *
+ * tsg_test_plan_gather_windows: csrc/gather.h plan_gather_windows, the CPU
+ * model of gather.hip's window passes, on plain arrays -- the candidate list
+ * as three parallel arrays (duplicates and any order allowed), the per-file
+ * flag words, whether the rule set has a mode-1 rule, and the windowable byte
+ * per row of the rule table.  cls (nfiles: 0 none, 1 whole, 2 windowed),
+ * first_run (nfiles: the run holding the file's first chunk or UINT32_MAX),
+ * marks (may be NULL; one byte per chunk of the segment), the run table as
+ * tsg_test_plan_gather's.
+ * tsg_test_windowable_rows: that byte table for a rule set (rules, then
+ * exclude-block pseudo-rules).
+ * tsg_test_regex_examined: the anchored run of `pattern` at text[pos] on the
+ * text cut at len, by the capture path (submatch != 0) or the match-end path,
+ * with the furthest byte index it asked for (len: the end of the text).
+ * tsg_scan_device_model_opts: tsg_scan_device_model_release with windows --
+ * the table model's candidates, plan_gather_windows, every run copied into an
+ * allocation of exactly its bytes, the windowed confirmation, and the
+ * fallback round (plan_gather over the insufficient files, a buffer of
+ * exactly its size).  The result holds two gather records: 0 the windowed
+ * round (tsg_result_window_segment 0 adds the classes and the insufficient
+ * files), 1 the fallback's.  opts NULL or 0/0: tsg_scan_device_model_release.
+ * A tsg_scan_batch_device_opts result made with tsg_test_keep_raw and
+ * tsg_test_keep_gather on holds, when files fell back, one more record behind
+ * its segments' (index tsg_result_raw_segments - 1): the fallback round's
+ * gather over the batch's files -- need, goff into the round's one buffer, the
+ * run table with sources in the batch's frame, the bytes, the buffer's
+ * capacity and whether the guard pattern behind it was whole. */
+typedef struct {
+  uint32_t nfiles;
+  const uint8_t* cls;
+  const uint32_t* insufficient;    /* ascending file indices of the segment */
+  size_t ninsufficient;
+} tsg_window_segment;
+int tsg_test_plan_gather_windows(const uint64_t* offsets, uint32_t nfiles, uint32_t lead, const uint32_t* cand_files,
+                                 const uint32_t* cand_rules, const uint64_t* cand_starts, size_t ncands,
+                                 const uint32_t* fflags, int all, const uint8_t* windowable, uint32_t nrows,
+                                 uint32_t chunk, const tsg_device_scan_opts* opts, uint8_t* cls, uint32_t* first_run,
+                                 uint8_t* marks, uint64_t* runs, size_t runs_cap, size_t* nruns, uint64_t* total);
+int tsg_test_windowable_rows(const tsg_ruleset* rs, uint8_t* rows, size_t cap, size_t* nrows, size_t* nrules);
+int tsg_test_regex_examined(const char* pattern, const uint8_t* text, size_t len, size_t pos, int submatch, long* end,
+                            size_t* examined);
+int tsg_result_window_segment(const tsg_result* r, size_t k, tsg_window_segment* rec);
+int tsg_scan_device_model_opts(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* offsets, uint32_t nfiles,
+                               const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
+                               uint32_t chunk, const tsg_device_scan_opts* opts, void (*release)(void* user),
+                               void* user, tsg_result** out);
+
 /* CPU model of tsg_prepare_batch_device (csrc/prep.h: plan_prep, the device
  * pass stated sequentially with its per-byte rule: a byte of a binary .pyc is
  * kept iff it is printable and lies in a window of 5 printable bytes of its

@@ -3,6 +3,7 @@
 bench.py leg).
 
   python tools/device_scan_probe.py [--config 1|2] [--gb 1] [--steps 3] [--seed N]
+                                    [--windows 512,2048,8192] [--min-file 65536]
 
 For a config-1-shaped (lognormal source files) or config-2-shaped (log-uniform
 64 B - 64 MB files) batch of workload/synth.py held in HBM it prints one JSON
@@ -10,7 +11,12 @@ line: the resident rate (tsg_scan_batch_resident, with the host copy), the
 device-only rate (tsg_scan_batch_device, without), whether the findings are
 equal, the gather's files / bytes / runs / kernel ms, and the time of one
 hipMemcpyAsync of gather_bytes from device memory into pinned host memory on
-the same box -- the yardstick for the gather's direct stores."""
+the same box -- the yardstick for the gather's direct stores.  With --windows
+the device-only scan is also run with windows of each given size on either
+side of a candidate (tsg_scan_batch_device_opts, files below --min-file whole):
+"windows" then holds, per size, the step times and rate, whether the findings
+equal the resident scan's, the gathered bytes, the windowed files and runs, and
+the files and bytes of the fallback round."""
 import argparse
 import ctypes
 import json
@@ -52,6 +58,8 @@ def main():
     ap.add_argument("--gb", type=float, default=1.0)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--seed", type=int, default=0x71215EC7)
+    ap.add_argument("--windows", default="", help="window sizes in bytes (each side of a candidate), comma separated")
+    ap.add_argument("--min-file", type=int, default=65536, help="files below this many bytes are gathered whole")
     a = ap.parse_args()
     L = _lib.lib()
     corpus = synth.generate(int(a.gb * 1e9), seed=a.seed, sizes="lognormal" if a.config == 1 else "loguniform")
@@ -64,10 +72,14 @@ def main():
     eng = sc.engine()
     paths, lens, _keep = _lib.pack_paths(corpus.paths)
 
-    def scan(device_only):
+    def scan(device_only, window=None):
         res = ctypes.c_void_p()
         t0 = time.perf_counter()
-        if device_only:
+        if window is not None:
+            opts = _lib.scan_opts(window)
+            _lib.check(L.tsg_scan_batch_device_opts(eng, ctypes.c_void_p(d.data_ptr()), off.ctypes.data, nfiles, paths,
+                                                    lens, None, ctypes.byref(opts), ctypes.byref(res)))
+        elif device_only:
             _lib.check(L.tsg_scan_batch_device(eng, ctypes.c_void_p(d.data_ptr()), off.ctypes.data, nfiles, paths,
                                                lens, None, ctypes.byref(res)))
         else:
@@ -76,16 +88,20 @@ def main():
         return res, (time.perf_counter() - t0) * 1e3
 
     out = {}
-    for name, dev in (("resident", False), ("device_only", True)):
+    sizes = [int(x) for x in a.windows.split(",") if x]
+    runs = [("resident", False, None), ("device_only", True, None)]
+    runs += [("window_%d" % w, True, (w, w, a.min_file)) for w in sizes]
+    for name, dev, window in runs:
         times, js, st, gs = [], None, None, None
         for k in range(a.steps + 1):                    # the first step warms the lanes and buffers up
-            res, ms = scan(dev)
+            res, ms = scan(dev, window)
             if k:
                 times.append(ms)
             if k == a.steps:
                 js = _lib.result_json(res)
                 st = _lib.result_stats(res)
                 gs = _lib.result_gather_stats(res)
+                gs.update(_lib.result_gather_window_stats(res))
             L.tsg_result_free(res)
         out[name] = (times, js, st, gs)
     tr, jr, sr, _ = out["resident"]
@@ -106,8 +122,19 @@ def main():
         "d2h_copy_gbps": round(gd["gather_bytes"] / 1e6 / copy_ms, 1) if copy_ms else None,
         "gather_over_copy": round(gd["gather_ms"] / copy_ms, 2) if copy_ms else None,
     }
+    line["windows"] = []
+    for w in sizes:
+        tw, jw, sw, gw = out["window_%d" % w]
+        line["windows"].append({
+            "before": w, "after": w, "min_file": a.min_file, "ms": [round(x, 3) for x in tw],
+            "gbps": round(gb / (min(tw) / 1e3), 1), "findings_equal": jw == jr,
+            "gather_files": gw["gather_files"], "gather_bytes": gw["gather_bytes"], "gather_runs": gw["gather_runs"],
+            "gather_share_of_batch": round(gw["gather_bytes"] / max(nbytes, 1), 4), "gather_ms": round(gw["gather_ms"], 3),
+            "window_files": gw["window_files"], "window_runs": gw["window_runs"], "window_bytes": gw["window_bytes"],
+            "fallback_files": gw["fallback_files"], "fallback_bytes": gw["fallback_bytes"],
+            "fallback_share_of_windowed": round(gw["fallback_files"] / max(gw["fallback_files"] + gw["window_files"], 1), 4)})
     print(json.dumps(line), flush=True)
-    return 0 if line["findings_equal"] else 1
+    return 0 if line["findings_equal"] and all(x["findings_equal"] for x in line["windows"]) else 1
 
 
 if __name__ == "__main__":

@@ -51,6 +51,16 @@ class TsgGatherSegment(ctypes.Structure):
                 ("bytes", ctypes.c_void_p)]
 
 
+class TsgDeviceScanOpts(ctypes.Structure):
+    _fields_ = [("window_before", ctypes.c_uint32), ("window_after", ctypes.c_uint32),
+                ("window_min_file", ctypes.c_uint64)]
+
+
+class TsgWindowSegment(ctypes.Structure):
+    _fields_ = [("nfiles", ctypes.c_uint32), ("cls", ctypes.c_void_p), ("insufficient", ctypes.c_void_p),
+                ("ninsufficient", ctypes.c_size_t)]
+
+
 class TsgStats(ctypes.Structure):
     _fields_ = [("k1_ms", ctypes.c_double), ("k2_ms", ctypes.c_double), ("h2d_ms", ctypes.c_double),
                 ("d2h_ms", ctypes.c_double), ("host_ms", ctypes.c_double), ("total_ms", ctypes.c_double),
@@ -94,6 +104,26 @@ SIGNATURES = [
     ("tsg_scan_batch_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                               c_char_pp, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.POINTER(ctypes.c_void_p)]),
+    ("tsg_scan_batch_device_opts", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                   c_char_pp, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.POINTER(TsgDeviceScanOpts), ctypes.POINTER(ctypes.c_void_p)]),
+    ("tsg_result_gather_window_stats", ctypes.c_int, [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_uint64)] * 5),
+    ("tsg_test_plan_gather_windows", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                                     ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
+                                                     ctypes.POINTER(TsgDeviceScanOpts), ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                     ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint64)]),
+    ("tsg_test_windowable_rows", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                 ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),
+    ("tsg_test_regex_examined", ctypes.c_int, [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
+                                                ctypes.c_int, ctypes.POINTER(ctypes.c_long),
+                                                ctypes.POINTER(ctypes.c_size_t)]),
+    ("tsg_result_window_segment", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(TsgWindowSegment)]),
+    ("tsg_scan_device_model_opts", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                   c_char_pp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                   ctypes.POINTER(TsgDeviceScanOpts), ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.POINTER(ctypes.c_void_p)]),
     ("tsg_result_gather_stats", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
                                                 ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                                                 ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint32)]),
@@ -422,6 +452,22 @@ def result_stats(res):
     st = TsgStats()
     check(lib().tsg_result_stats(res, ctypes.byref(st)))
     return {k: getattr(st, k) for k, _ in TsgStats._fields_}
+
+
+def scan_opts(window):
+    """tsg_device_scan_opts from window = (before, after, min_file), or None (no windows)."""
+    if window is None:
+        return None
+    before, after, min_file = window
+    return TsgDeviceScanOpts(int(before), int(after), int(min_file))
+
+
+def result_gather_window_stats(res):
+    """What the windows of a tsg_scan_batch_device_opts result took (tsg_result_gather_window_stats)."""
+    v = [ctypes.c_uint64() for _ in range(5)]
+    check(lib().tsg_result_gather_window_stats(res, *[ctypes.byref(x) for x in v]))
+    names = ("window_files", "window_runs", "window_bytes", "fallback_files", "fallback_bytes")
+    return {k: x.value for k, x in zip(names, v)}
 
 
 def result_gather_stats(res):

@@ -208,7 +208,7 @@ void tsg_free_pinned(void* p);
 
 static int do_scan(tsg_engine* e, const void* d_data, const uint8_t* h_data, const uint64_t* offsets,
                    uint32_t nfiles, const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
-                   tsg_result** out, bool device_only = false) {
+                   tsg_result** out, bool device_only = false, const GatherWindowOpts* win = nullptr) {
   if (!e || !out || !offsets || (nfiles && !paths) || (!h_data && nfiles && !device_only))
     return fail(TSG_ERR_INVALID, "NULL argument");
   BatchInput in;
@@ -223,14 +223,15 @@ static int do_scan(tsg_engine* e, const void* d_data, const uint8_t* h_data, con
   r->rs = e->eng->ruleset();
   std::string err;
   if (!e->eng->keep_raw() && !(device_only && e->eng->keep_gather())) {
-    if (!e->eng->scan(in, &r->files, &r->stats, &err)) { delete r; return fail(TSG_ERR_HIP, err); }
+    if (!e->eng->scan(in, &r->files, &r->stats, &err, nullptr, win)) { delete r; return fail(TSG_ERR_HIP, err); }
   } else {
     // test hook (tsg_test_keep_raw): the segments' GPU outputs beside the findings
     RawScan raw;
-    if (!e->eng->scan(in, &r->files, &r->stats, &err, &raw)) { delete r; return fail(TSG_ERR_HIP, err); }
+    if (!e->eng->scan(in, &r->files, &r->stats, &err, &raw, win)) { delete r; return fail(TSG_ERR_HIP, err); }
     r->cands = std::move(raw.cands);
     r->file_flags = std::move(raw.ff);
     r->raw_segs = std::move(raw.segs);
+    if (raw.has_fallback) r->raw_segs.push_back(std::move(raw.fallback));   // (behind the segments' records)
   }
   *out = r;
   return TSG_OK;
@@ -258,6 +259,31 @@ int tsg_scan_batch_device(tsg_engine* e, const void* d_data, const uint64_t* off
   TSG_API_TRY
   if (!d_data) return fail(TSG_ERR_INVALID, "d_data is NULL");
   return do_scan(e, d_data, nullptr, offsets, nfiles, paths, path_lens, binary, out, /*device_only=*/true);
+  TSG_API_CATCH
+}
+
+int tsg_scan_batch_device_opts(tsg_engine* e, const void* d_data, const uint64_t* offsets, uint32_t nfiles,
+                               const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
+                               const tsg_device_scan_opts* opts, tsg_result** out) {
+  TSG_API_TRY
+  if (!d_data) return fail(TSG_ERR_INVALID, "d_data is NULL");
+  GatherWindowOpts win;
+  if (opts) { win.before = opts->window_before; win.after = opts->window_after; win.min_file = opts->window_min_file; }
+  return do_scan(e, d_data, nullptr, offsets, nfiles, paths, path_lens, binary, out, /*device_only=*/true,
+                 win.on() ? &win : nullptr);
+  TSG_API_CATCH
+}
+
+int tsg_result_gather_window_stats(const tsg_result* r, uint64_t* window_files, uint64_t* window_runs,
+                                   uint64_t* window_bytes, uint64_t* fallback_files, uint64_t* fallback_bytes) {
+  TSG_API_TRY
+  if (!r) return fail(TSG_ERR_INVALID, "result is NULL");
+  if (window_files) *window_files = r->stats.window_files;
+  if (window_runs) *window_runs = r->stats.window_runs;
+  if (window_bytes) *window_bytes = r->stats.window_bytes;
+  if (fallback_files) *fallback_files = r->stats.fallback_files;
+  if (fallback_bytes) *fallback_bytes = r->stats.fallback_bytes;
+  return TSG_OK;
   TSG_API_CATCH
 }
 
@@ -1003,7 +1029,92 @@ int tsg_scan_device_model(const tsg_ruleset* rs, const uint8_t* data, const uint
 int tsg_scan_device_model_release(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* offsets, uint32_t nfiles,
                                   const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
                                   uint32_t chunk, void (*release)(void* user), void* user, tsg_result** out) {
+  return tsg_scan_device_model_opts(rs, data, offsets, nfiles, paths, path_lens, binary, chunk, nullptr, release, user, out);
+}
+
+int tsg_test_plan_gather_windows(const uint64_t* offsets, uint32_t nfiles, uint32_t lead, const uint32_t* cand_files,
+                                 const uint32_t* cand_rules, const uint64_t* cand_starts, size_t ncands,
+                                 const uint32_t* fflags, int all, const uint8_t* windowable, uint32_t nrows,
+                                 uint32_t chunk, const tsg_device_scan_opts* opts, uint8_t* cls, uint32_t* first_run,
+                                 uint8_t* marks, uint64_t* runs, size_t runs_cap, size_t* nruns, uint64_t* total) {
   TSG_API_TRY
+  if (!offsets || !fflags || !opts || !cls || !first_run || !nruns || !total || chunk == 0 || lead > nfiles ||
+      (ncands && (!cand_files || !cand_rules || !cand_starts)) || (nrows && !windowable))
+    return fail(TSG_ERR_INVALID, "bad argument");
+  for (uint32_t i = 0; i < nfiles; ++i)
+    if (offsets[i + 1] < offsets[i]) return fail(TSG_ERR_INVALID, "offsets must be non-decreasing");
+  std::vector<GatherCand> cands(ncands);
+  for (size_t k = 0; k < ncands; ++k) cands[k] = GatherCand{cand_files[k], cand_rules[k], cand_starts[k]};
+  GatherWindowOpts o;
+  o.before = opts->window_before; o.after = opts->window_after; o.min_file = opts->window_min_file;
+  GatherWindowPlan wp;
+  plan_gather_windows(offsets, nfiles, lead, cands.data(), ncands, fflags, all != 0, windowable, nrows, chunk, o, &wp);
+  std::copy(wp.cls.begin(), wp.cls.end(), cls);
+  std::copy(wp.first_run.begin(), wp.first_run.end(), first_run);
+  if (marks) std::copy(wp.marks.begin(), wp.marks.end(), marks);
+  *nruns = wp.runs.size();
+  *total = wp.total;
+  if (wp.runs.size() > runs_cap || (!runs && !wp.runs.empty())) return fail(TSG_ERR_INVALID, "run table too small");
+  for (size_t k = 0; k < wp.runs.size(); ++k) {
+    runs[3 * k] = wp.runs[k].src; runs[3 * k + 1] = wp.runs[k].dst; runs[3 * k + 2] = wp.runs[k].len;
+  }
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_test_windowable_rows(const tsg_ruleset* rs, uint8_t* rows, size_t cap, size_t* nrows, size_t* nrules) {
+  TSG_API_TRY
+  if (!rs || !nrows) return fail(TSG_ERR_INVALID, "NULL argument");
+  std::string err;
+  const std::shared_ptr<const Prefilter> pfp = model_prefilter(rs->rs, &err);
+  if (!pfp) return fail(TSG_ERR_INTERNAL, err);
+  const std::vector<uint8_t> w = Engine::create_model(rs->rs, *pfp)->windowable_rows();
+  *nrows = w.size();
+  if (nrules) *nrules = rs->rs->rules.size();
+  if (rows) std::copy(w.begin(), w.begin() + std::min(cap, w.size()), rows);
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_test_regex_examined(const char* pattern, const uint8_t* text, size_t len, size_t pos, int submatch, long* end,
+                            size_t* examined) {
+  TSG_API_TRY
+  if (!pattern || (!text && len) || !end || !examined) return fail(TSG_ERR_INVALID, "NULL argument");
+  std::string err;
+  const std::unique_ptr<re::Regexp> rx = re::Regexp::compile(pattern, &err);
+  if (!rx) return fail(TSG_ERR_CONFIG, err);
+  if (pos > len) return fail(TSG_ERR_INVALID, "pos is past the text");
+  const uint8_t* t = text ? text : reinterpret_cast<const uint8_t*>("");
+  if (submatch) {
+    std::vector<re::Cap> caps(2 * (rx->num_subexp() + 1), -1);
+    *end = rx->match_at_examined(t, len, pos, caps.data(), examined) ? static_cast<long>(caps[1]) : -1;
+  } else {
+    *end = rx->match_end_examined(t, len, pos, examined);
+  }
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_result_window_segment(const tsg_result* r, size_t k, tsg_window_segment* rec) {
+  TSG_API_TRY
+  if (!r || !rec) return fail(TSG_ERR_INVALID, "NULL argument");
+  if (k >= r->raw_segs.size()) return fail(TSG_ERR_INVALID, "no such segment");
+  const RawSegment& s = r->raw_segs[k];
+  rec->nfiles = static_cast<uint32_t>(s.cls.size());
+  rec->cls = s.cls.data();
+  rec->insufficient = s.insufficient.data();
+  rec->ninsufficient = s.insufficient.size();
+  return TSG_OK;
+  TSG_API_CATCH
+}
+
+int tsg_scan_device_model_opts(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* offsets, uint32_t nfiles,
+                               const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
+                               uint32_t chunk, const tsg_device_scan_opts* opts, void (*release)(void* user),
+                               void* user, tsg_result** out) {
+  TSG_API_TRY
+  GatherWindowOpts win;
+  if (opts) { win.before = opts->window_before; win.after = opts->window_after; win.min_file = opts->window_min_file; }
   if (!rs || !out || !offsets || (nfiles && (!paths || !data)) || chunk == 0) return fail(TSG_ERR_INVALID, "NULL argument");
   std::string err;
   // an engine without devices for this call, around the models' compiled prefilter
@@ -1021,7 +1132,7 @@ int tsg_scan_device_model_release(const tsg_ruleset* rs, const uint8_t* data, co
   r->rs = rs->rs;
   RawScan raw;
   const std::function<void()> before_confirm = [&] { if (release) release(user); };
-  if (!eng->model_scan_device(in, chunk, &r->files, &r->stats, &err, &raw, &before_confirm))
+  if (!eng->model_scan_device(in, chunk, &r->files, &r->stats, &err, &raw, &before_confirm, win.on() ? &win : nullptr))
     return fail(TSG_ERR_INTERNAL, err);
   r->raw_segs = std::move(raw.segs);
   *out = r.release();

@@ -6,8 +6,10 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
 #include <stdexcept>
 #include <thread>
 #include <type_traits>
@@ -36,8 +38,18 @@ void Engine::release_call(CallCtx* cc) {
   free_calls_.push_back(cc);
 }
 
+std::vector<uint8_t> Engine::windowable_rows() const {
+  std::vector<uint8_t> w(pf_.rules.size(), 0);
+  for (size_t r = 0; r < pf_.rules.size() && r < rs_->rules.size(); ++r)
+    w[r] = (pf_.rules[r].mode == 0 || pf_.rules[r].mode == 4) && pf_.rules[r].gate_on_gpu;
+  return w;
+}
+
+static_assert(sizeof(GatherCand) == sizeof(Cand) && offsetof(GatherCand, start) == offsetof(Cand, start) &&
+              offsetof(GatherCand, rule) == offsetof(Cand, rule), "plan_gather_windows reads the host's candidates");
+
 bool Engine::model_scan_device(const BatchInput& in, uint32_t chunk, SecretVec* results, ScanStats* st, std::string* err,
-                               RawScan* raw, const std::function<void()>* before_confirm) {
+                               RawScan* raw, const std::function<void()>* before_confirm, const GatherWindowOpts* win) {
   if (!in.h_data || !in.offsets || !in.paths || chunk == 0) { *err = "model_scan_device: NULL argument"; return false; }
   const uint32_t nfiles = in.nfiles;
   const uint64_t total = nfiles ? in.offsets[nfiles] : 0;
@@ -60,6 +72,7 @@ bool Engine::model_scan_device(const BatchInput& in, uint32_t chunk, SecretVec* 
       for (uint64_t s : cand[r]) g.cands.push_back(Cand{f, static_cast<uint32_t>(r), s});
     need[f] = all || g.ff[f] || std::any_of(cand.begin(), cand.end(), [](const std::vector<uint64_t>& v) { return !v.empty(); });
   }
+  if (win && win->on()) return model_scan_windows(in, chunk, g, all, *win, results, st, err, raw, before_confirm);
   // the gather: plan_gather's layout, the runs copied byte for byte into a
   // buffer of exactly gather_total bytes (so a read outside a run is a read
   // outside an allocation)
@@ -116,6 +129,141 @@ bool Engine::model_scan_device(const BatchInput& in, uint32_t chunk, SecretVec* 
   return true;
 }
 
+// model_scan_device with windows: g holds the table model's GPU outputs.
+bool Engine::model_scan_windows(const BatchInput& in, uint32_t chunk, SegmentOut& g, bool all, const GatherWindowOpts& win,
+                                SecretVec* results, ScanStats* st, std::string* err, RawScan* raw,
+                                const std::function<void()>* before_confirm) {
+  const uint32_t nfiles = in.nfiles;
+  const uint64_t total = nfiles ? in.offsets[nfiles] : 0;
+  const std::vector<uint8_t> wrows = windowable_rows();
+  GatherWindowPlan wp;
+  plan_gather_windows(in.offsets, nfiles, 0, reinterpret_cast<const GatherCand*>(g.cands.data()), g.cands.size(),
+                      g.ff.data(), all, wrows.data(), static_cast<uint32_t>(wrows.size()), chunk, win, &wp);
+  // every run in an allocation of exactly its bytes
+  std::vector<std::vector<uint8_t>> run_bytes(wp.runs.size());
+  for (size_t k = 0; k < wp.runs.size(); ++k) {
+    run_bytes[k].assign(in.h_data + wp.runs[k].src, in.h_data + wp.runs[k].src + wp.runs[k].len);
+    g.run_base.push_back(run_bytes[k].data());
+  }
+  g.gathered = true;
+  g.windowed = true;
+  g.gather_total = wp.total;
+  g.gcls = wp.cls;
+  g.wruns = wp.runs;
+  // the fallback's gather is planned and copied here, while the batch may
+  // still be read: over every windowed file, of which the round takes its own
+  std::vector<uint8_t> wneed(nfiles, 0);
+  for (uint32_t f = 0; f < nfiles; ++f) wneed[f] = wp.cls[f] == kGatherClassWindow;
+  std::vector<std::vector<uint8_t>> whole_bytes(nfiles);
+  for (uint32_t f = 0; f < nfiles; ++f)
+    if (wneed[f]) {
+      const uint64_t src = in.offsets[f] / chunk * chunk;
+      whole_bytes[f].assign(in.h_data + src, in.h_data + in.offsets[f + 1]);
+    }
+  Segment sg;
+  sg.in = in;
+  sg.in.h_data = nullptr;
+  sg.bytes = total;
+  if (before_confirm && *before_confirm) (*before_confirm)();
+  results->clear();
+  results->resize(nfiles);
+  uint64_t nconf = 0, nfind = 0;
+  GatherPlan fp;
+  std::vector<uint8_t> fbuf;
+  std::vector<uint32_t> insufficient;
+  std::vector<uint64_t> goff1;               // the windowed round's (the fallback round replaces g.goff)
+  CallCtx* cc = acquire_call();
+  try {
+    confirm_segment(*cc, sg, g, results->data(), &nconf, &nfind, false);
+    insufficient = g.insufficient;
+    goff1 = g.goff;
+    if (!insufficient.empty()) {
+      std::vector<uint8_t> need(nfiles, 0);
+      for (uint32_t f : insufficient) need[f] = 1;
+      plan_gather(in.offsets, nfiles, 0, need.data(), chunk, &fp);
+      fbuf.assign(fp.total, 0);
+      // (a run of adjacent insufficient files: each file's bytes from its own copy)
+      for (uint32_t f : insufficient) {
+        const uint64_t head = in.offsets[f] % chunk;
+        const uint64_t d0 = fp.goff[f] - head;
+        // the head bytes only where this file starts a run (else they are the previous file's)
+        const bool first = f == 0 || !need[f - 1];
+        const uint8_t* sp = whole_bytes[f].data();
+        if (first) std::memcpy(fbuf.data() + d0, sp, whole_bytes[f].size());
+        else std::memcpy(fbuf.data() + fp.goff[f], sp + head, whole_bytes[f].size() - head);
+      }
+      confirm_fallback(*cc, sg, g, fp, fbuf.data(), results->data(), &nconf, &nfind);
+    }
+  } catch (const std::exception& x) {
+    release_call(cc);
+    *err = x.what();
+    return false;
+  }
+  release_call(cc);
+  if (st) {
+    *st = ScanStats();
+    st->bytes = total;
+    st->files = nfiles;
+    st->confirm_files = nconf;
+    st->findings = nfind;
+    st->chunk_bytes = chunk;
+    st->gather_files = g.gather_files;
+    st->gather_bytes = wp.total + fp.total;
+    st->gather_runs = wp.runs.size() + fp.runs.size();
+    st->window_files = g.window_files;
+    st->window_runs = wp.runs.size();
+    st->window_bytes = wp.total;
+    st->fallback_files = insufficient.size();
+    st->fallback_bytes = fp.total;
+  }
+  if (raw) {
+    *raw = RawScan();
+    raw->segs.resize(2);
+    RawSegment& rec = raw->segs[0];
+    rec.nfiles = nfiles;
+    rec.bytes = total;
+    rec.chunk = chunk;
+    rec.cls = wp.cls;
+    rec.need.assign(nfiles, 0);
+    for (uint32_t f = 0; f < nfiles; ++f) rec.need[f] = wp.cls[f] != kGatherClassNone;
+    rec.goff = goff1;
+    rec.runs = wp.runs;
+    rec.gather_total = wp.total;
+    rec.gathered.assign(wp.total, 0);
+    for (size_t k = 0; k < wp.runs.size(); ++k)
+      std::memcpy(rec.gathered.data() + wp.runs[k].dst, run_bytes[k].data(), wp.runs[k].len);
+    rec.insufficient = insufficient;
+    RawSegment& fb = raw->segs[1];
+    fb.nfiles = nfiles;
+    fb.bytes = total;
+    fb.chunk = chunk;
+    fb.need.assign(nfiles, 0);
+    for (uint32_t f : insufficient) fb.need[f] = 1;
+    fb.goff = fp.goff;
+    fb.goff.resize(nfiles, kGatherNone);
+    fb.runs = fp.runs;
+    fb.gather_total = fp.total;
+    fb.gathered = fbuf;
+  }
+  return true;
+}
+
+void Engine::confirm_fallback(CallCtx& cc, const Segment& sg, SegmentOut& g, const GatherPlan& gp, const uint8_t* gbase,
+                              Secret* results, uint64_t* nconf, uint64_t* nfind) {
+  g.work = g.insufficient;
+  g.light.clear();
+  g.insufficient.clear();
+  g.windowed = false;
+  g.run_base.clear();
+  g.goff = gp.goff;
+  g.gbase = gbase;
+  g.gather_total = gp.total;
+  const uint64_t files = g.gather_files, wfiles = g.window_files;
+  confirm_segment(cc, sg, g, results, nconf, nfind, false);
+  g.gather_files = files;                  // (the first round's count stands: these files were among them)
+  g.window_files = wfiles - g.work.size();
+}
+
 // Host confirmation of one segment (files [0, in.nfiles) of sg.in, results
 // into results[0..nfiles)) from that segment's GPU output `g`.
 void Engine::plan_confirm(const Segment& sg, SegmentOut* gp) const {
@@ -169,13 +317,16 @@ namespace {
 // (std::false_type), or a device-only scan's gather buffer through the
 // device's goff (std::true_type).  The confirm worker is instantiated once per
 // source, so neither pays a branch per file for the other.
+struct FromWindows {};     // a device-only scan's gather with windows: whole files through goff, the rest through runs
 struct ConfirmBytes {
   const uint8_t* h;
   const uint64_t* off;
   const uint8_t* gbuf;
   const uint64_t* goff;
+  const uint8_t* const* fptr;     // FromWindows, the CPU model: per whole file, its bytes in its run's allocation
   const uint8_t* content(std::false_type, uint32_t f) const { return h + off[f]; }
   const uint8_t* content(std::true_type, uint32_t f) const { return gbuf + goff[f]; }
+  const uint8_t* content(FromWindows, uint32_t f) const { return fptr ? fptr[f] : gbuf + goff[f]; }
   // K1's newline counts are per chunk of the segment's frame; prefix_at also
   // reads the bytes between the chunk boundary below the file and the file
   void newlines(std::false_type, uint32_t f, uint32_t, NlSource* n) const {
@@ -190,6 +341,12 @@ struct ConfirmBytes {
     n->data_off = off[f] - head;
     n->file_off = off[f];
   }
+  void newlines(FromWindows, uint32_t f, uint32_t chunk, NlSource* n) const {
+    const uint64_t head = off[f] % chunk;
+    n->data = content(FromWindows(), f) - head;
+    n->data_off = off[f] - head;
+    n->file_off = off[f];
+  }
 };
 
 }  // namespace
@@ -201,8 +358,27 @@ void Engine::confirm_segment(CallCtx& cc, const Segment& sg, SegmentOut& g, Secr
   const size_t nplan = pf_.rules.size();   // rules + exclude-block pseudo-rules
   const auto t_begin = std::chrono::steady_clock::now();
   if (!g.planned) plan_confirm(sg, &g);
-  const ConfirmBytes src{in.h_data, in.offsets, g.gbase, g.goff.data()};
-  if (g.gathered) {
+  if (g.gathered && g.windowed) prepare_windows(sg, &g);
+  // (the CPU model's runs live in allocations of their own: a whole file's
+  // bytes are then addressed through a per-file pointer into its run's)
+  std::vector<const uint8_t*> file_base;
+  if (g.gathered && g.windowed && !g.run_base.empty()) {
+    file_base.assign(in.nfiles, reinterpret_cast<const uint8_t*>(""));
+    for (uint32_t f = sg.lead; f < in.nfiles; ++f) {
+      if (g.gcls[f] != kGatherClassWhole) continue;
+      const uint32_t k = gather_run_of(g.wruns.data(), g.wruns.size(), in.offsets[f] / g.chunk * g.chunk);
+      if (k != kGatherNoRun) file_base[f] = g.run_base[k] + (in.offsets[f] - g.wruns[k].src);   // (else: empty, past the last chunk)
+    }
+  }
+  const ConfirmBytes src{in.h_data, in.offsets, g.gbase, g.goff.data(), file_base.empty() ? nullptr : file_base.data()};
+  if (g.gathered && g.windowed) {
+    uint64_t nf = 0, nw = 0;
+    for (uint32_t f = sg.lead; f < in.nfiles; ++f) { nf += g.gcls[f] != kGatherClassNone; nw += g.gcls[f] == kGatherClassWindow; }
+    g.gather_files = nf;
+    g.window_files = nw;
+    for (uint32_t f : g.work)
+      if (g.gcls[f] == kGatherClassNone) throw std::runtime_error("device-only scan: a file the confirmer reads was not gathered");
+  } else if (g.gathered) {
     // a file to confirm that the device did not gather (or placed outside
     // what it gathered) fails the call: it is never scanned from wrong bytes
     if (g.goff.size() != in.nfiles || (!g.gbase && g.gather_total)) throw std::runtime_error("device-only scan: no gather for the segment");
@@ -255,9 +431,15 @@ void Engine::confirm_segment(CallCtx& cc, const Segment& sg, SegmentOut& g, Secr
       }
     }
   };
+  std::mutex short_mu;
+  g.insufficient.clear();
+  // run k's bytes
+  auto run_ptr = [&](uint32_t k) { return g.run_base.empty() ? g.gbase + g.wruns[k].dst : g.run_base[k]; };
   auto worker = [&](auto from) {               // from: where the bytes are (ConfirmBytes)
     FilePlan plan;
     std::vector<std::vector<uint64_t>> spare;
+    std::vector<WindowRun> wruns;
+    std::vector<uint32_t> my_short;            // windowed files found insufficient
     // per-thread counts and work taken a few files at a time: 15 threads
     // hitting shared counters once per file serialised on their cache lines
     uint64_t my_conf = 0, my_find = 0, my_plan = 0, my_scan = 0, my_store = 0;
@@ -270,7 +452,7 @@ void Engine::confirm_segment(CallCtx& cc, const Segment& sg, SegmentOut& g, Secr
         wend = std::min<uint32_t>(wi + kTake, static_cast<uint32_t>(work.size()));
       }
       uint32_t f = work[wi++];
-      if (confirm_prefetch_ && wi < wend) {
+      if (confirm_prefetch_ && wi < wend && !std::is_same<decltype(from), FromWindows>::value) {
         // the next file of this take: its result slot and the text at its
         // first candidate starts, fetched while this file is confirmed (the
         // host has not touched the batch's bytes since they were written):
@@ -292,7 +474,8 @@ void Engine::confirm_segment(CallCtx& cc, const Segment& sg, SegmentOut& g, Secr
       const auto tp0 = prof ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
       const char* path_p = in.paths[f];
       const size_t path_n = in.path_lens ? in.path_lens[f] : std::strlen(path_p);
-      const uint8_t* content = src.content(from, f);
+      const bool in_windows = std::is_same<decltype(from), FromWindows>::value && g.gcls[f] == kGatherClassWindow;
+      const uint8_t* content = in_windows ? nullptr : src.content(from, f);
       const size_t len = in.offsets[f + 1] - in.offsets[f];
       const bool binary = in.binary ? in.binary[f] != 0 : false;
       const uint32_t cb = per_file[f], ce = per_file[f + 1];
@@ -349,6 +532,32 @@ void Engine::confirm_segment(CallCtx& cc, const Segment& sg, SegmentOut& g, Secr
           else { plan.active.push_back(y); ++b; }
         }
       }
+      if (in_windows) {
+        // the file's runs: from the one holding its head chunk on
+        wruns.clear();
+        const uint64_t o0 = in.offsets[f], o1 = in.offsets[f + 1];
+        for (uint32_t k = gather_run_of(g.wruns.data(), g.wruns.size(), o0 / g.chunk * g.chunk);
+             k != kGatherNoRun && k < g.wruns.size() && g.wruns[k].src < o1; ++k) {
+          const GatherRun& r = g.wruns[k];
+          const uint64_t a = std::max(r.src, o0), b = std::min(r.src + r.len, o1);
+          if (b <= a) continue;
+          wruns.push_back(WindowRun{a - o0, b - o0, run_ptr(k) + (a - r.src)});
+        }
+        WindowFile wf;
+        wf.runs = wruns.data();
+        wf.nruns = wruns.size();
+        wf.len = len;
+        wf.chunk_nl = g.nl.data();
+        wf.chunk = g.chunk;
+        wf.file_off = o0;
+        bool insufficient = wruns.empty() || wruns[0].a != 0;
+        Secret s;
+        if (!insufficient) s = scan_file_windows(rs, path_p, path_n, wf, binary, plan, &insufficient);
+        if (insufficient) { --my_conf; my_short.push_back(f); continue; }
+        my_find += s.findings().size();
+        results[f] = std::move(s);
+        continue;
+      }
       NlSource nls;
       nls.chunk_nl = g.nl.data();
       src.newlines(from, f, g.chunk, &nls);
@@ -367,6 +576,10 @@ void Engine::confirm_segment(CallCtx& cc, const Segment& sg, SegmentOut& g, Secr
     }
     nconf.fetch_add(my_conf);
     nfind.fetch_add(my_find);
+    if (!my_short.empty()) {
+      std::lock_guard<std::mutex> lk(short_mu);
+      g.insufficient.insert(g.insufficient.end(), my_short.begin(), my_short.end());
+    }
     if (prof) { ph_plan += my_plan; ph_scan += my_scan; ph_store += my_store; }
   };
   // small confirmations (a few files, little text: per-file Scan batches) run
@@ -385,7 +598,8 @@ void Engine::confirm_segment(CallCtx& cc, const Segment& sg, SegmentOut& g, Secr
   auto body = [&](int idx) {
     if (idx >= active) return;
     auto a = std::chrono::steady_clock::now();
-    if (g.gathered) worker(std::true_type());
+    if (g.gathered && g.windowed) worker(FromWindows());
+    else if (g.gathered) worker(std::true_type());
     else worker(std::false_type());
     auto b = std::chrono::steady_clock::now();
     light_files();
@@ -404,8 +618,46 @@ void Engine::confirm_segment(CallCtx& cc, const Segment& sg, SegmentOut& g, Secr
                  light_us.load() / 1e3, active, ph_plan.load() / 1e6, ph_scan.load() / 1e6, ph_store.load() / 1e6,
                  ph[0] / 1e6, ph[1] / 1e6, ph[2] / 1e6, ph[3] / 1e6, ph[4] / 1e6);
   }
+  std::sort(g.insufficient.begin(), g.insufficient.end());
   *nconf_out += nconf.load();
   *nfind_out += nfind.load();
+}
+
+// The windowed gather's tables as they came from the device, checked before
+// anything is indexed with them, and goff for the files gathered whole.
+void Engine::prepare_windows(const Segment& sg, SegmentOut* gp) const {
+  SegmentOut& g = *gp;
+  const BatchInput& in = sg.in;
+  const uint64_t total = in.nfiles ? in.offsets[in.nfiles] : 0;
+  if (g.gcls.size() != in.nfiles || g.chunk == 0 || (!g.gbase && g.run_base.empty() && g.gather_total))
+    throw std::runtime_error("device-only scan: no windowed gather for the segment");
+  if (!g.run_base.empty() && g.run_base.size() != g.wruns.size())
+    throw std::runtime_error("device-only scan: run allocations do not match the run table");
+  uint64_t src_end = 0, dst_end = 0;
+  for (const GatherRun& r : g.wruns) {
+    if (r.len == 0 || r.src < src_end || r.src % g.chunk != 0 || r.len > total || r.src > total - r.len ||
+        r.dst < dst_end || r.dst % kGatherAlign != 0 || r.len > g.gather_total || r.dst > g.gather_total - r.len)
+      throw std::runtime_error("device-only scan: a gather run outside the segment or the buffer");
+    src_end = r.src + r.len;
+    dst_end = r.dst + r.len;
+  }
+  g.goff.assign(in.nfiles, kGatherNone);
+  for (uint32_t f = sg.lead; f < in.nfiles; ++f) {
+    if (g.gcls[f] > kGatherClassWindow) throw std::runtime_error("device-only scan: a file class out of range");
+    if (g.gcls[f] == kGatherClassNone) continue;
+    g.goff[f] = 0;
+    if (g.gcls[f] != kGatherClassWhole) continue;
+    const uint64_t o0 = in.offsets[f], o1 = in.offsets[f + 1], c0 = o0 / g.chunk * g.chunk;
+    const uint32_t k = c0 < total ? gather_run_of(g.wruns.data(), g.wruns.size(), c0) : kGatherNoRun;
+    if (k == kGatherNoRun) {
+      if (o1 != o0 || c0 < total) throw std::runtime_error("device-only scan: a whole file's run is missing");
+      g.goff[f] = g.gather_total;
+      continue;
+    }
+    const GatherRun& r = g.wruns[k];
+    if (o1 > r.src + r.len) throw std::runtime_error("device-only scan: a whole file reaches past its run");
+    g.goff[f] = r.dst + (o0 - r.src);
+  }
 }
 
 }  // namespace tsg

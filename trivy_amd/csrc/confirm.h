@@ -7,6 +7,7 @@
 #include <memory>
 #include <vector>
 
+#include "gather.h"
 #include "threadpool.h"
 
 namespace tsg {
@@ -29,6 +30,18 @@ struct SegmentOut {
   bool gathered = false;
   uint64_t gather_total = 0, gather_files = 0;
   std::vector<uint64_t> goff;
+  // ... with windows (tsg_device_scan_opts; gather.h plan_gather_windows): the
+  // run table and the files' classes instead of goff, which confirm_segment
+  // derives for the whole files.  run_base (the CPU model only): run k's
+  // bytes are at run_base[k], an allocation of their own, not at gbase + dst.
+  // insufficient (out): the windowed files whose confirmation would have read
+  // outside their runs, ascending; they have no result yet.
+  bool windowed = false;
+  std::vector<uint8_t> gcls;
+  std::vector<GatherRun> wruns;
+  std::vector<const uint8_t*> run_base;
+  std::vector<uint32_t> insufficient;
+  uint64_t window_files = 0;
   // the confirmation's plan (plan_confirm): candidates grouped per file, the
   // files to confirm (largest first) and the rest.  (Built on the driver
   // thread it delayed the next piece's launch by as much as it saved the

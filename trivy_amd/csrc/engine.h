@@ -51,6 +51,11 @@ struct ScanStats {
   uint64_t gather_files = 0, gather_bytes = 0, gather_runs = 0;
   double gather_ms = 0;
   uint32_t gather_retries = 0;
+  // ... with windows (tsg_device_scan_opts): files confirmed from windows, the
+  // windowed layouts' runs and bytes (whole files' among them), and the files
+  // and bytes of the fallback round (files fetched whole after all).
+  // gather_bytes and gather_runs hold both rounds.
+  uint64_t window_files = 0, window_runs = 0, window_bytes = 0, fallback_files = 0, fallback_bytes = 0;
 };
 
 // A batch scan stage: results[i] = Scan(ScanArgs{paths[i], data[off[i]:off[i+1]],
@@ -85,6 +90,11 @@ struct RawSegment {
   std::vector<uint64_t> gather_caps;    // the buffer's capacity at each copy launch
   std::vector<uint8_t> guard_ok;        // per launch: the 0xA5 pattern past that capacity was still whole
   std::vector<uint8_t> gathered;        // gather_total bytes of the buffer
+  // ... with windows: the files' classes (gather.h kGatherClass*; goff then
+  // holds the whole files' offsets as the host derived them) and the files
+  // found insufficient (segment file indices)
+  std::vector<uint8_t> cls;
+  std::vector<uint32_t> insufficient;
 };
 // K1's per-chunk and per-file outputs of one prefilter_only call (tests).
 struct PrefilterRaw {
@@ -100,6 +110,12 @@ struct RawScan {
   std::vector<std::vector<std::vector<uint64_t>>> cands;   // [file][rule]; a file without candidates has no rule lists
   std::vector<uint32_t> ff;
   std::string error;                    // a candidate outside its segment's files or the rule table
+  // device-only scans with windows and tsg_test_keep_gather on: the fallback
+  // round's gather as it came back -- the run table in the batch's frame (src)
+  // and the round's one buffer (dst), its bytes, capacity and guard; need and
+  // goff over the batch's files (goff: in that buffer)
+  bool has_fallback = false;
+  RawSegment fallback;
 };
 
 struct DeviceTables;
@@ -128,7 +144,9 @@ class Engine {
 
   // results[i] is Scanner.Scan(ScanArgs{paths[i], data[off[i]:off[i+1]], binary[i]}).
   // raw (tests only, tsg_test_keep_raw): receives the segments' GPU outputs.
-  bool scan(const BatchInput& in, SecretVec* results, ScanStats* stats, std::string* err, RawScan* raw = nullptr);
+  // win (device-only scans): gather windows around candidates (gather.h); NULL or off: whole files.
+  bool scan(const BatchInput& in, SecretVec* results, ScanStats* stats, std::string* err, RawScan* raw = nullptr,
+            const GatherWindowOpts* win = nullptr);
 
   // Only the two GPU passes (no host confirmation): used by tests to compare
   // raw candidates ([file][rule], exclude-block pseudo-rules after the rules,
@@ -205,8 +223,17 @@ class Engine {
   // before_confirm (optional) runs once the gather is made and before the
   // confirmation: nothing reads in.h_data after it (a sanitizer run frees the
   // batch there).
+  // win on: plan_gather_windows' layout, every run copied into an allocation
+  // of its own (a read past a run is a read outside an allocation), the
+  // windowed confirmation, and the fallback round over the insufficient files
+  // (raw->segs[0]: the first round; raw->segs[1]: the fallback's gather).
   bool model_scan_device(const BatchInput& in, uint32_t chunk, SecretVec* results, ScanStats* stats, std::string* err,
-                         RawScan* raw = nullptr, const std::function<void()>* before_confirm = nullptr);
+                         RawScan* raw = nullptr, const std::function<void()>* before_confirm = nullptr,
+                         const GatherWindowOpts* win = nullptr);
+  // one byte per row of the prefilter's rule table: a candidate of that row
+  // can be confirmed from a window (an anchored or reverse-anchored rule whose
+  // keyword gate is exact on the GPU; no exclude-block pseudo-rule)
+  std::vector<uint8_t> windowable_rows() const;
 
   const Prefilter& prefilter() const { return pf_; }
   std::shared_ptr<const Ruleset> ruleset() const { return rs_; }
@@ -224,7 +251,10 @@ class Engine {
   bool run_segment(DeviceTables& dt, Lane& ln, const Segment& sg, const void* d_data, const uint64_t* d_off_up,
                    ScanStats* st, GpuOut* out, std::string* err, const std::function<void()>* while_gpu = nullptr,
                    K1Chain* chain = nullptr, bool defer_copy = false, const StageIn* stage = nullptr,
-                   bool gather = false);
+                   bool gather = false, const GatherWindowOpts* win = nullptr);
+  bool fallback_round(const BatchInput& in, const std::vector<Segment>& segs, DeviceTables& dt, CallCtx& cc,
+                      std::vector<std::pair<size_t, SegmentOut>>* short_segs, SecretVec* results, ScanStats* st,
+                      uint64_t* nconf, uint64_t* nfind, uint64_t* nwindow, RawScan* raw, std::string* err);
   // run_segment's phases (SegRun: what they share)
   bool seg_geometry(SegRun& r, GpuOut* out, std::string* err);
   bool seg_stage_offsets(SegRun& r, std::string* err);
@@ -244,8 +274,16 @@ class Engine {
   friend struct SegmentDriver;                           // a scan's device driver (engine.hip)
   friend struct WireFeed;                                // takes and returns the engine's packers
   void plan_confirm(const Segment& sg, SegmentOut* g) const;
+  void prepare_windows(const Segment& sg, SegmentOut* g) const;
+  bool model_scan_windows(const BatchInput& in, uint32_t chunk, SegmentOut& g, bool all, const GatherWindowOpts& win,
+                          SecretVec* results, ScanStats* st, std::string* err, RawScan* raw,
+                          const std::function<void()>* before_confirm);
   void confirm_segment(CallCtx& cc, const Segment& sg, SegmentOut& g, Secret* results, uint64_t* nconf,
                        uint64_t* nfind, bool gpu_in_flight);
+  // g's insufficient files again, from a gather of those whole files
+  // (plan_gather's goff over the segment, the buffer at gbase)
+  void confirm_fallback(CallCtx& cc, const Segment& sg, SegmentOut& g, const GatherPlan& gp, const uint8_t* gbase,
+                        Secret* results, uint64_t* nconf, uint64_t* nfind);
   Lane* acquire_lane(DeviceTables& dt, std::string* err);
   void release_lane(DeviceTables& dt, Lane* ln);
   bool tar_gather(DeviceTables& dt, Lane* ln, const uint8_t* d_tar, uint64_t len, uint64_t* cap_blocks,

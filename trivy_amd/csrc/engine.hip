@@ -1466,6 +1466,8 @@ struct DeviceTables {
   DevBuf<uint16_t> v_next;
   DevBuf<uint8_t> v_cls;
   uint32_t kw_words = 1;
+  DevBuf<uint8_t> wrows;                       // device-only scans with windows: the windowable byte per rule-table row
+  uint32_t nrows = 0;
   std::mutex mu;                               // guards the lane pool and lds_set
   std::vector<std::pair<const void*, int>> lds_set;   // K1 builds whose dynamic-LDS limit is set (per device)
   std::vector<std::unique_ptr<Lane>> lanes;
@@ -1700,6 +1702,9 @@ struct Lane : LaneStreams {
   DevBuf<uint64_t> d_goff, d_gmeta;
   DevBuf<GatherRun> d_gruns;
   PinnedBuf rb_need, rb_goff, rb_gruns, rb_gmeta;
+  // ... with windows: the passes' scratch (gather_dev.h) and the files' classes
+  DevBuf<uint8_t> d_gw, d_gcls;
+  PinnedBuf rb_gcls;
   size_t gather_cap = 0;
   size_t hit_cap = 1 << 20, cand_cap = 1 << 18, over_cap = 1 << 18;
   double k2_maxr_per_byte = 0;                       // K2 grid of the next segment: the last one's fullest region
@@ -1733,13 +1738,19 @@ struct GpuOut : SegmentOut {
   const uint8_t* rb_need = nullptr;
   const GatherRun* rb_gruns = nullptr;
   size_t n_goff = 0, n_need = 0, n_gruns = 0;
+  const uint8_t* rb_gcls = nullptr;              // with windows: the classes; the run table is then always kept
+  size_t n_gcls = 0;
   void finish_copy() {
     if (!deferred) return;
     cands.resize(n_cands);                       // (CandDev -> Cand: the one conversion, see the static_assert)
     if (n_cands) std::memcpy(cands.data(), rb_cands, n_cands * sizeof(Cand));
     ff.assign(rb_ff, rb_ff + n_ff);
     nl.assign(rb_nl, rb_nl + n_nl);
-    if (gathered) {
+    if (gathered && windowed) {
+      gcls.assign(rb_gcls, rb_gcls + n_gcls);
+      wruns.assign(rb_gruns, rb_gruns + n_gruns);
+      if (!gather_caps.empty()) gruns = wruns;   // (tsg_test_keep_gather)
+    } else if (gathered) {
       goff.assign(rb_goff, rb_goff + n_goff);
       need.assign(rb_need, rb_need + n_need);
       gruns.assign(rb_gruns, rb_gruns + n_gruns);
@@ -2024,6 +2035,7 @@ void add_stats(ScanStats* a, const ScanStats& s) {
   a->blocks_split += s.blocks_split;
   a->gather_bytes += s.gather_bytes; a->gather_runs += s.gather_runs; a->gather_ms += s.gather_ms;
   a->gather_retries += s.gather_retries;
+  a->window_runs += s.window_runs; a->window_bytes += s.window_bytes;
 }
 
 }  // namespace
@@ -2099,6 +2111,9 @@ std::unique_ptr<Engine> Engine::create(std::shared_ptr<const Ruleset> rs, const 
     std::unique_ptr<DeviceTables> dt(new DeviceTables());
     dt->device = d;
     if (!build_tables(e->pf_, dt.get(), err)) return nullptr;
+    const std::vector<uint8_t> wrows = e->windowable_rows();
+    dt->nrows = static_cast<uint32_t>(wrows.size());
+    if (!dt->wrows.upload(wrows, err)) return nullptr;
     e->dev_.push_back(std::move(dt));
   }
   return e;
@@ -2242,6 +2257,8 @@ struct SegRun {
   // device-only scans: gather the confirmer's files behind K2 (lead: files never gathered)
   bool gather = false, keep_gather = false;
   uint32_t lead = 0;
+  const GatherWindowOpts* win = nullptr;      // ... in windows (gather.h plan_gather_windows)
+  size_t runs_cap = 0;                        // the run table's room at the last gather launch
 };
 
 namespace {
@@ -2336,8 +2353,10 @@ bool Engine::seg_size_scratch(SegRun& r, std::string* err) {
          // deferred-output slots: kOutSlots per thread (x2 grid slack)
          ln.d_ob.ensure(static_cast<size_t>(sms) * 1024 * 2 * kOutSlots, err) &&
          (!file_index_ || !r.nfidx || ln.d_fidx.ensure(r.nfidx, err)) &&
-         (!r.gather || (ln.d_need.ensure(in.nfiles, err) && ln.d_goff.ensure(in.nfiles, err) &&
-                        ln.d_gruns.ensure((static_cast<size_t>(in.nfiles) + 1) / 2 + 1, err) && ln.d_gmeta.ensure(2, err)));
+         (!r.gather || r.win || (ln.d_need.ensure(in.nfiles, err) && ln.d_goff.ensure(in.nfiles, err) &&
+                        ln.d_gruns.ensure((static_cast<size_t>(in.nfiles) + 1) / 2 + 1, err) && ln.d_gmeta.ensure(2, err))) &&
+         (!r.win || (ln.d_gw.ensure(gather_windows_scratch_bytes(r.nchunks, in.nfiles), err) &&
+                     ln.d_gcls.ensure(in.nfiles, err) && ln.d_gmeta.ensure(2, err)));
 }
 
 // K1's grid for this attempt, and the prologue: keyword bits, file flags,
@@ -2543,11 +2562,22 @@ bool Engine::seg_readback_wait(SegRun& r, int a2, std::string* err) {
     // the gather's layout rides the same round trip (a launch of its own:
     // tsg_readback's region list is full); need and the run table only for
     // tsg_test_keep_gather
-    if (!ln.rb_gmeta.ensure_readback(16, err) || !ln.rb_goff.ensure_readback(nfiles * sizeof(uint64_t), err)) return false;
+    if (!ln.rb_gmeta.ensure_readback(16, err)) return false;
     Readbacks rg;
     rg.add(ln.d_gmeta.p, ln.rb_gmeta, 4);
-    rg.add(ln.d_goff.p, ln.rb_goff, 2ull * nfiles);
-    if (r.keep_gather) {
+    if (r.win) {
+      // with windows: the files' classes and the run table (the host places the files from it)
+      if (!ln.rb_gcls.ensure_readback(nfiles, err) || !ln.rb_gruns.ensure_readback(r.runs_cap * sizeof(GatherRun), err))
+        return false;
+      rg.add(ln.d_gcls.p, ln.rb_gcls, (nfiles + 3) / 4);
+      rg.add(ln.d_gruns.p, ln.rb_gruns, r.runs_cap * (sizeof(GatherRun) / 4),
+             reinterpret_cast<const uint32_t*>(ln.d_gmeta.p), sizeof(GatherRun) / 4);
+    } else if (!ln.rb_goff.ensure_readback(nfiles * sizeof(uint64_t), err)) {
+      return false;
+    } else {
+      rg.add(ln.d_goff.p, ln.rb_goff, 2ull * nfiles);
+    }
+    if (r.keep_gather && !r.win) {
       const size_t max_runs = (static_cast<size_t>(nfiles) + 1) / 2 + 1;
       if (!ln.rb_need.ensure_readback(nfiles, err) || !ln.rb_gruns.ensure_readback(max_runs * sizeof(GatherRun), err))
         return false;
@@ -2612,9 +2642,19 @@ bool Engine::seg_launch_gather(SegRun& r, GpuOut* out, std::string* err) {
   for (auto& e : ln.gev) if (!e) HIP_OK(hipEventCreate(&e));
   bool all = false;
   for (const auto& pr : pf_.rules) all = all || pr.mode == 1;
+  if (r.win) {
+    // every run holds a head or whole file or a candidate's window: at most one per file and stored candidate
+    r.runs_cap = static_cast<size_t>(std::min<uint64_t>((r.nchunks + 1) / 2 + 1,
+                                                        static_cast<uint64_t>(r.in.nfiles) + ln.cand_cap + 1));
+    if (!ln.d_gruns.ensure(r.runs_cap, err)) return false;
+  }
   HIP_OK(hipEventRecord(ln.gev[0], s));
-  if (!gather_plan_launch(ln.d_cands.p, ln.d_cnt.p + 1, static_cast<uint32_t>(ln.cand_cap), ln.d_ff.p, r.d_off,
-                          r.in.nfiles, r.lead, all, r.chunk, ln.d_need.p, ln.d_goff.p, ln.d_gruns.p, ln.d_gmeta.p, s, err) ||
+  if (!(r.win ? gather_windows_launch(ln.d_cands.p, ln.d_cnt.p + 1, static_cast<uint32_t>(ln.cand_cap), ln.d_ff.p, r.d_off,
+                                      r.in.nfiles, r.lead, all, r.dt.wrows.p, r.dt.nrows, r.chunk, r.total, *r.win,
+                                      gather_windows_scratch_layout(ln.d_gw.p, r.nchunks, r.in.nfiles), ln.d_gcls.p,
+                                      ln.d_gruns.p, r.runs_cap, ln.d_gmeta.p, s, err)
+              : gather_plan_launch(ln.d_cands.p, ln.d_cnt.p + 1, static_cast<uint32_t>(ln.cand_cap), ln.d_ff.p, r.d_off,
+                          r.in.nfiles, r.lead, all, r.chunk, ln.d_need.p, ln.d_goff.p, ln.d_gruns.p, ln.d_gmeta.p, s, err)) ||
       !gather_copy_launch(r.d_data, ln.d_gruns.p, ln.d_gmeta.p, static_cast<uint8_t*>(out->gather.b->mem.d),
                           out->gather.cap(), static_cast<uint32_t>(std::max(r.dt.sms, 1)) * 8u, s, err))
     return false;
@@ -2637,6 +2677,7 @@ bool Engine::seg_gather_retry(SegRun& r, GpuOut* out, std::string* err) {
     out->gather_caps.push_back(out->gather.cap());
     out->guard_ok.push_back(whole ? 1 : 0);
   };
+  if (r.win && nruns > r.runs_cap) { *err = "gather windows: more runs than files and candidates"; return false; }
   float ms = 0;
   HIP_OK(hipEventElapsedTime(&ms, ln.gev[0], ln.gev[1]));
   note();
@@ -2661,9 +2702,19 @@ bool Engine::seg_gather_retry(SegRun& r, GpuOut* out, std::string* err) {
   ln.gather_cap = std::max(ln.gather_cap, out->gather.cap());
   out->gathered = true;
   out->gather_total = total;
-  out->rb_goff = ln.rb_goff.as<uint64_t>();
-  out->n_goff = r.in.nfiles;
-  if (r.keep_gather) {
+  if (r.win) {
+    out->windowed = true;
+    out->rb_gcls = ln.rb_gcls.as<uint8_t>();
+    out->n_gcls = r.in.nfiles;
+    out->rb_gruns = ln.rb_gruns.as<GatherRun>();
+    out->n_gruns = static_cast<size_t>(nruns);
+    r.st->window_bytes += total;
+    r.st->window_runs += nruns;
+  } else {
+    out->rb_goff = ln.rb_goff.as<uint64_t>();
+    out->n_goff = r.in.nfiles;
+  }
+  if (r.keep_gather && !r.win) {
     out->rb_need = ln.rb_need.as<uint8_t>();
     out->n_need = r.in.nfiles;
     out->rb_gruns = ln.rb_gruns.as<GatherRun>();
@@ -2749,8 +2800,10 @@ bool Engine::fold_k2_stats(Lane& ln, std::string* err) {
 // seen afterwards, grown, and the pass run again.
 bool Engine::run_segment(DeviceTables& dt, Lane& ln, const Segment& sg, const void* d_data, const uint64_t* d_off_up,
                          ScanStats* st, GpuOut* out, std::string* err, const std::function<void()>* while_gpu,
-                         K1Chain* chain, bool defer_copy, const StageIn* stage_in, bool gather) {
+                         K1Chain* chain, bool defer_copy, const StageIn* stage_in, bool gather,
+                         const GatherWindowOpts* win) {
   SegRun r{dt, ln, sg.in, st, chain};
+  r.win = gather && win && win->on() ? win : nullptr;
   // device-only scans: a failed call gives its gather buffer back to the pool
   // with `out`, which another scan may take (or free to grow it) at once, so
   // nothing queued here may still be storing into it when this returns false
@@ -3645,6 +3698,7 @@ struct ScanCall {
   bool resident = false;
   bool dual = false;                   // resident batches of several pieces: two drivers on the device (K1Chain)
   bool device_only = false;            // resident without a host copy: the GPU gathers the confirmer's files
+  const GatherWindowOpts* win = nullptr;   // ... in windows around the candidates
   K1Chain chain;
   const uint8_t* h_dev = nullptr;      // a direct batch: the device view of its pinned bytes
   bool wire_want = false;
@@ -3748,7 +3802,7 @@ struct SegmentDriver {
     if (!eng.run_segment(*dt, *ln, sg, resident ? sg.in.d_data : ln->ring[slot].p,
                          resident ? nullptr : ln->off_slot[slot].p, &sst, &job->out, &e, &plan_fn,
                          sc.dual ? &sc.chain : nullptr, /*defer_copy=*/true, direct ? &stage : nullptr,
-                         /*gather=*/sc.device_only))
+                         /*gather=*/sc.device_only, sc.win))
       return false;
     if (wf) wf->segment_done();        // this segment's ring slot may be written again
     else if (!resident) sst.wire_bytes += sg.bytes;
@@ -3850,6 +3904,95 @@ struct SegmentDriver {
   }
 };
 
+// Device-only scans with windows, the fallback round: the files whose windows
+// did not suffice (short_segs: their segments' outputs) are laid out whole by
+// plan_gather, segment by segment, one behind the other in one gather buffer;
+// one tsg_gather_copy from the batch brings them, and each segment's files
+// are confirmed as a device-only scan without windows confirms.
+bool Engine::fallback_round(const BatchInput& in, const std::vector<Segment>& segs, DeviceTables& dt, CallCtx& cc,
+                            std::vector<std::pair<size_t, SegmentOut>>* short_segs, SecretVec* results, ScanStats* st,
+                            uint64_t* nconf, uint64_t* nfind, uint64_t* nwindow, RawScan* raw, std::string* err) {
+  const bool keep = raw && keep_gather();
+  std::vector<GatherPlan> plans(short_segs->size());
+  std::vector<uint64_t> base(short_segs->size(), 0);
+  std::vector<GatherRun> runs;
+  uint64_t total = 0, nfiles = 0;
+  for (size_t i = 0; i < short_segs->size(); ++i) {
+    const Segment& sg = segs[(*short_segs)[i].first];
+    const SegmentOut& g = (*short_segs)[i].second;
+    std::vector<uint8_t> need(sg.in.nfiles, 0);
+    for (uint32_t f : g.insufficient) {
+      if (f < sg.lead || f >= sg.in.nfiles) { *err = "fallback round: a file outside its segment"; return false; }
+      need[f] = 1;
+    }
+    plan_gather(sg.in.offsets, sg.in.nfiles, sg.lead, need.data(), g.chunk, &plans[i]);
+    // the segment's frame in the batch's (a segment is a 16-byte aligned sub-range of the batch)
+    const uint64_t frame = static_cast<uint64_t>(static_cast<const uint8_t*>(sg.in.d_data) - static_cast<const uint8_t*>(in.d_data));
+    base[i] = total;
+    for (const GatherRun& r : plans[i].runs) runs.push_back(GatherRun{frame + r.src, total + r.dst, r.len});
+    total += plans[i].total;
+    nfiles += g.insufficient.size();
+  }
+  HIP_OK(hipSetDevice(dt.device));
+  Lane* ln = acquire_lane(dt, err);
+  if (!ln) return false;
+  GatherLease lease;
+  bool ok = false;
+  const uint64_t meta[2] = {runs.size(), total};   // (read by the upload until the stream is drained below)
+  do {
+    if (!ln->d_gruns.ensure(runs.size(), err) || !ln->d_gmeta.ensure(2, err) || !lease.take(dt, total, err)) break;
+    if (keep) std::memset(lease.host() + lease.cap(), 0xA5, kGatherGuard);
+    if (hipMemcpyAsync(ln->d_gruns.p, runs.data(), runs.size() * sizeof(GatherRun), hipMemcpyHostToDevice, ln->compute) != hipSuccess ||
+        hipMemcpyAsync(ln->d_gmeta.p, meta, sizeof(meta), hipMemcpyHostToDevice, ln->compute) != hipSuccess) {
+      *err = "fallback round: run table upload failed";
+      break;
+    }
+    if (!gather_copy_launch(static_cast<const uint8_t*>(in.d_data), ln->d_gruns.p, ln->d_gmeta.p,
+                            static_cast<uint8_t*>(lease.b->mem.d), lease.cap(),
+                            static_cast<uint32_t>(std::max(dt.sms, 1)) * 8u, ln->compute, err))
+      break;
+    if (hipStreamSynchronize(ln->compute) != hipSuccess) { *err = "fallback round: the copy failed"; break; }
+    ok = true;
+  } while (false);
+  if (!ok) (void)hipStreamSynchronize(ln->compute);
+  release_lane(dt, ln);
+  if (!ok) return false;
+  if (keep) {                                       // tsg_test_keep_gather: before the confirmation, as the segments' records
+    RawSegment& rec = raw->fallback;
+    raw->has_fallback = true;
+    rec.nfiles = in.nfiles;
+    rec.bytes = in.offsets[in.nfiles];
+    rec.need.assign(in.nfiles, 0);
+    rec.goff.assign(in.nfiles, kGatherNone);
+    for (size_t i = 0; i < short_segs->size(); ++i) {
+      const Segment& sg = segs[(*short_segs)[i].first];
+      for (uint32_t f : (*short_segs)[i].second.insufficient) {
+        rec.need[sg.f0 + f - sg.lead] = 1;
+        rec.goff[sg.f0 + f - sg.lead] = base[i] + plans[i].goff[f];
+      }
+    }
+    rec.runs = runs;
+    rec.gather_total = total;
+    rec.gather_caps.push_back(lease.cap());
+    bool whole = true;
+    for (size_t k = 0; k < kGatherGuard; ++k) whole = whole && lease.host()[lease.cap() + k] == 0xA5;
+    rec.guard_ok.push_back(whole ? 1 : 0);
+    rec.gathered.assign(lease.host(), lease.host() + total);
+  }
+  for (size_t i = 0; i < short_segs->size(); ++i) {
+    const Segment& sg = segs[(*short_segs)[i].first];
+    SegmentOut& g = (*short_segs)[i].second;
+    const uint64_t nshort = g.insufficient.size();
+    confirm_fallback(cc, sg, g, plans[i], lease.host() + base[i], results->data() + sg.f0, nconf, nfind);
+    *nwindow -= nshort;
+  }
+  st->fallback_files = nfiles;
+  st->fallback_bytes = total;
+  st->gather_bytes += total;
+  st->gather_runs += runs.size();
+  return true;
+}
+
 // One batch through the pipeline:
 //  * uploaded data (h_data only): the batch is cut into segments of about
 //    the policy's segment bytes at file boundaries; each device's driver
@@ -3863,7 +4006,8 @@ struct SegmentDriver {
 // Every segment is a self-contained batch (offsets rebased to 0, data a
 // 16-byte aligned sub-range; segments.h), so the kernels are unchanged and the
 // result is the one-segment result.
-bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::string* err, RawScan* raw) {
+bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::string* err, RawScan* raw,
+                  const GatherWindowOpts* win) {
   ScanStats local;
   if (!st) st = &local;
   *st = ScanStats();
@@ -3915,6 +4059,10 @@ bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::
   sc.resident = resident;
   sc.dual = dual;
   sc.device_only = resident && !in.h_data;
+  sc.win = sc.device_only && win && win->on() ? win : nullptr;
+  // with windows: the segments that have insufficient files, kept for the fallback round
+  std::vector<std::pair<size_t, SegmentOut>> short_segs;
+  uint64_t nwindow = 0;
   for (const Segment& sg : segs) {
     sc.max_seg = std::max(sc.max_seg, sg.bytes);
     sc.max_seg_files = std::max<size_t>(sc.max_seg_files, sg.in.nfiles);
@@ -3955,13 +4103,37 @@ bool Engine::scan(const BatchInput& in, SecretVec* results, ScanStats* st, std::
         // (drivers that block on an event leave every core to the pool)
         confirm_segment(*cc, sg, job.out, results->data() + sg.f0, &nconf, &nfind, left > 0 && !dual);
         ngather += job.out.gather_files;
+        if (job.out.windowed) {
+          nwindow += job.out.window_files;
+          if (raw) {
+            RawSegment& rec = raw->segs[job.seg];
+            rec.cls = job.out.gcls;
+            rec.goff = job.out.goff;
+            rec.insufficient = job.out.insufficient;
+          }
+          // (the base alone: the segment's gather buffer goes back to its pool with the job)
+          if (!job.out.insufficient.empty())
+            short_segs.emplace_back(job.seg, SegmentOut(std::move(static_cast<SegmentOut&>(job.out))));
+        }
         sc.confirmer_idle.store(true, std::memory_order_release);
         host_ms += ms_since(th);
         if (host_profile_) std::fprintf(stderr, "[tsg tl] seg %zu confirm %.3f-%.3f ms\n", job.seg, c_start, ms_since(sc.t_feed0));
       },
       pop_spin_us_, &run_err);
+  if (run_ok && !short_segs.empty()) {
+    const auto th = std::chrono::steady_clock::now();
+    bool ok = false;
+    try {
+      ok = fallback_round(in, segs, *drivers[0], *cc, &short_segs, results, st, &nconf, &nfind, &nwindow, raw, &run_err);
+    } catch (const std::exception& x) {
+      run_err = x.what();
+    }
+    host_ms += ms_since(th);
+    if (!ok) { release_call(cc); *err = run_err; return false; }
+  }
   release_call(cc);
   if (!run_ok) { *err = run_err; return false; }
+  st->window_files = nwindow;
   if (raw) {
     if (!raw->error.empty()) { *err = raw->error; return false; }
     for (auto& f : raw->cands)

@@ -14,7 +14,28 @@
 //                     spread over the whole grid
 // The destination is host-mapped coherent memory; the stores go over the link
 // themselves (as tsg_readback's), with no copy engine and no second round trip.
+//
+// With windows (tsg_device_scan_opts; gather.h plan_gather_windows is the CPU
+// model, pass for pass) the layout is made on the segment's K1 chunk grid:
+//   tsg_gw_flags     per candidate: its file has one; it needs the whole file
+//                    (a row that is not windowable, a start at or past the
+//                    file's length -- kFullScanStart among them)
+//   tsg_gw_class     per file: none / whole / windowed before the windows are
+//                    counted; a windowed file's head chunk is marked
+//   tsg_gw_windows   per candidate of a windowed file: its window's chunks
+//   tsg_gw_count     per marked chunk: one more for every windowed file on it
+//   tsg_gw_demote    per file: windows on more than half of its chunks -> whole
+//   tsg_gw_fill      per chunk: marked when a whole file lies on it
+//   tsg_gw_regions   per region of 128 chunks: its marked chunks and run starts
+//   tsg_prep_scan    twice (region_scan_launch): the regions' prefixes
+//   tsg_gw_runs      one wave per region: each run start's (src, dst), each
+//                    run end's last byte
+//   tsg_gw_finish    per run: its length; the totals
+// and the copy is tsg_gather_copy over that run table.  Every index that
+// comes from a candidate is bounded before it is used: the file by [lead,
+// nfiles), the start by the file's length, the chunks by the file's own.
 #include "gather_dev.h"
+#include "prep_dev.h"
 
 namespace tsg {
 namespace {
@@ -132,6 +153,203 @@ __global__ __launch_bounds__(256) void tsg_gather_copy(const uint8_t* __restrict
   }
 }
 
+
+// ---------------------------------------------------------------- windows
+constexpr uint32_t kGwRegion = 128;          // chunks per region (one wave, two chunks per lane)
+constexpr uint32_t kGwWaves = 4;
+
+__global__ __launch_bounds__(256) void tsg_gw_flags(const uint4* __restrict__ cands, const uint32_t* __restrict__ ncands,
+                                                    uint32_t cand_cap, const uint64_t* __restrict__ off,
+                                                    uint32_t nfiles, uint32_t lead,
+                                                    const uint8_t* __restrict__ wrows, uint32_t nrows,
+                                                    uint8_t* __restrict__ any, uint8_t* __restrict__ whole) {
+  const uint32_t tid = blockIdx.x * 256 + threadIdx.x, step = gridDim.x * 256;
+  const uint32_t n = min(*ncands, cand_cap);       // (as tsg_gather_mark: an overflowed list is run again)
+  for (uint32_t i = tid; i < n; i += step) {
+    const uint4 c = cands[i];
+    const uint32_t f = c.x, rule = c.y;
+    if (f < lead || f >= nfiles) continue;
+    any[f] = 1;
+    const uint64_t start = c.z | (static_cast<uint64_t>(c.w) << 32);
+    const uint64_t len = off[f + 1] - off[f];
+    if (rule >= nrows || wrows[rule] == 0 || start >= len) whole[f] = 1;
+  }
+}
+
+__global__ __launch_bounds__(256) void tsg_gw_class(const uint64_t* __restrict__ off, uint32_t nfiles, uint32_t lead,
+                                                    const uint32_t* __restrict__ fflags, uint32_t all,
+                                                    uint64_t min_file, const uint8_t* __restrict__ any,
+                                                    const uint8_t* __restrict__ whole, uint8_t* __restrict__ cls,
+                                                    uint8_t* __restrict__ marks, uint32_t chunk, uint64_t nchunks) {
+  const uint32_t tid = blockIdx.x * 256 + threadIdx.x, step = gridDim.x * 256;
+  for (uint32_t f = lead + tid; f < nfiles; f += step) {
+    const uint64_t o = off[f], len = off[f + 1] - o;
+    const bool special = all || fflags[f] != 0;
+    uint8_t c = kGatherClassNone;
+    if (special || any[f]) {
+      const bool w = special || whole[f] || len < min_file || len == 0;
+      c = w ? kGatherClassWhole : kGatherClassWindow;
+      if (!w && o / chunk < nchunks) marks[o / chunk] = 1;     // (len > 0: the chunk exists)
+    }
+    cls[f] = c;
+  }
+}
+
+__global__ __launch_bounds__(256) void tsg_gw_windows(const uint4* __restrict__ cands,
+                                                      const uint32_t* __restrict__ ncands, uint32_t cand_cap,
+                                                      const uint64_t* __restrict__ off, uint32_t nfiles, uint32_t lead,
+                                                      const uint8_t* __restrict__ cls, uint8_t* __restrict__ whole,
+                                                      uint8_t* __restrict__ marks, uint32_t chunk, uint64_t nchunks,
+                                                      uint32_t before, uint32_t after) {
+  const uint32_t tid = blockIdx.x * 256 + threadIdx.x, step = gridDim.x * 256;
+  const uint32_t n = min(*ncands, cand_cap);
+  for (uint32_t i = tid; i < n; i += step) {
+    const uint4 c = cands[i];
+    const uint32_t f = c.x;
+    if (f < lead || f >= nfiles || cls[f] != kGatherClassWindow) continue;
+    const uint64_t start = c.z | (static_cast<uint64_t>(c.w) << 32);
+    const uint64_t o = off[f], len = off[f + 1] - o;
+    if (start >= len) continue;                    // (tsg_gw_flags made such a file whole: never reached)
+    uint64_t lo, hi;
+    window_chunks(o, len, start, before, after, chunk, &lo, &hi);
+    const uint64_t c0 = o / chunk, c1 = (o + len - 1) / chunk;
+    // (window_chunks clips to the file: c0 <= lo <= hi <= c1 < nchunks; checked all the same)
+    if (lo < c0 || hi > c1 || hi >= nchunks || lo > hi) { whole[f] = 1; continue; }
+    if (2 * (hi - lo + 1) > c1 - c0 + 1) { whole[f] = 1; continue; }
+    for (uint64_t k = lo; k <= hi; ++k) marks[k] = 1;
+  }
+}
+
+// the first file at or above lead that ends above byte b (nfiles: none)
+__device__ __forceinline__ uint32_t first_file_ending_above(const uint64_t* __restrict__ off, uint32_t nfiles,
+                                                            uint32_t lead, uint64_t b) {
+  uint32_t lo = lead, hi = nfiles;
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (off[mid + 1] > b) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(256) void tsg_gw_count(const uint8_t* __restrict__ marks, uint64_t nchunks,
+                                                    const uint64_t* __restrict__ off, uint32_t nfiles, uint32_t lead,
+                                                    const uint8_t* __restrict__ cls, uint32_t* __restrict__ cnt,
+                                                    uint32_t chunk) {
+  const uint64_t tid = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x, step = static_cast<uint64_t>(gridDim.x) * 256;
+  for (uint64_t c = tid; c < nchunks; c += step) {
+    if (!marks[c]) continue;
+    const uint64_t b0 = c * chunk, b1 = b0 + chunk;
+    for (uint32_t f = first_file_ending_above(off, nfiles, lead, b0); f < nfiles && off[f] < b1; ++f)
+      if (cls[f] == kGatherClassWindow && off[f + 1] > off[f]) atomicAdd(cnt + f, 1u);
+  }
+}
+
+__global__ __launch_bounds__(256) void tsg_gw_demote(const uint64_t* __restrict__ off, uint32_t nfiles, uint32_t lead,
+                                                     uint8_t* __restrict__ cls, const uint8_t* __restrict__ whole,
+                                                     const uint32_t* __restrict__ cnt, uint8_t* __restrict__ marks,
+                                                     uint32_t chunk, uint64_t nchunks) {
+  const uint32_t tid = blockIdx.x * 256 + threadIdx.x, step = gridDim.x * 256;
+  for (uint32_t f = lead + tid; f < nfiles; f += step) {
+    const uint64_t o = off[f], len = off[f + 1] - o;
+    uint8_t c = cls[f];
+    if (c == kGatherClassWindow) {
+      const uint64_t nfc = (o + len - 1) / chunk - o / chunk + 1;
+      if (whole[f] || 2 * static_cast<uint64_t>(cnt[f]) > nfc) cls[f] = c = kGatherClassWhole;
+    }
+    // an empty whole file: the chunk it lies in (tsg_gw_fill sees only files with bytes)
+    if (c == kGatherClassWhole && len == 0 && o / chunk < nchunks) marks[o / chunk] = 1;
+  }
+}
+
+__global__ __launch_bounds__(256) void tsg_gw_fill(uint8_t* __restrict__ marks, uint64_t nchunks,
+                                                   const uint64_t* __restrict__ off, uint32_t nfiles, uint32_t lead,
+                                                   const uint8_t* __restrict__ cls, uint32_t chunk) {
+  const uint64_t tid = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x, step = static_cast<uint64_t>(gridDim.x) * 256;
+  for (uint64_t c = tid; c < nchunks; c += step) {
+    if (marks[c]) continue;
+    const uint64_t b0 = c * chunk, b1 = b0 + chunk;
+    for (uint32_t f = first_file_ending_above(off, nfiles, lead, b0); f < nfiles && off[f] < b1; ++f)
+      if (cls[f] == kGatherClassWhole && off[f + 1] > off[f]) { marks[c] = 1; break; }
+  }
+}
+
+// one thread per region: its 128 mark bytes (0 or 1), and the run starts among them
+__global__ __launch_bounds__(256) void tsg_gw_regions(const uint8_t* __restrict__ marks, uint32_t nregions,
+                                                      uint32_t* __restrict__ region_m, uint32_t* __restrict__ region_s) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= nregions) return;
+  const uint64_t b0 = static_cast<uint64_t>(r) * kGwRegion;
+  const v4u* p = reinterpret_cast<const v4u*>(marks + b0);
+  uint32_t prev = r ? marks[b0 - 1] : 0u, m = 0, s = 0;
+#pragma unroll
+  for (uint32_t q = 0; q < kGwRegion / 16; ++q) {
+    const v4u w = p[q];
+    const uint32_t d[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint32_t x = d[k] & 0x01010101u;
+      // a start: a marked byte whose predecessor is not (bytes shifted up by one, the carry from the word before)
+      const uint32_t pred = (x << 8) | prev;
+      m += __popc(x);
+      s += __popc(x & ~pred);
+      prev = x >> 24;
+    }
+  }
+  region_m[r] = m;
+  region_s[r] = s;
+}
+
+// One wave per region, lane l on chunks 2l and 2l + 1 of it.  Run k is the
+// k-th run start in chunk order; it lands behind the marked chunks in front
+// of it.  A run's end stores its last byte + 1 into len (tsg_gw_finish
+// subtracts src).  Nothing is stored at or past runs_cap.
+__global__ __launch_bounds__(256) void tsg_gw_runs(const uint8_t* __restrict__ marks, uint32_t nregions,
+                                                   const uint64_t* __restrict__ base_m,
+                                                   const uint64_t* __restrict__ base_s, GatherRun* __restrict__ runs,
+                                                   uint64_t runs_cap, uint32_t chunk, uint64_t total) {
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint32_t r = blockIdx.x * kGwWaves + wv;
+  if (r >= nregions) return;                 // whole waves only; no workgroup barrier below
+  const uint64_t b0 = static_cast<uint64_t>(r) * kGwRegion;
+  const uint32_t m = reinterpret_cast<const uint16_t*>(marks + b0)[lane];
+  const uint32_t m0 = m & 1u, m1 = (m >> 8) & 1u;
+  // (the marks array ends with a region of zeros: b0 + 128 is readable)
+  const uint32_t before = r ? marks[b0 - 1] & 1u : 0u, behind = marks[b0 + kGwRegion] & 1u;
+  const uint32_t up = __shfl_up(m1, 1), down = __shfl_down(m0, 1);
+  const uint32_t prev = lane ? up : before, next = lane < 63 ? down : behind;
+  const uint32_t s0 = m0 & ~prev & 1u, s1 = m1 & ~m0 & 1u;
+  const uint32_t e0 = m0 & ~m1 & 1u, e1 = m1 & ~next & 1u;
+  uint32_t im = m0 + m1, is = s0 + s1;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const uint32_t um = __shfl_up(im, d), us = __shfl_up(is, d);
+    if (lane >= d) { im += um; is += us; }
+  }
+  const uint64_t xm = base_m[r] + (im - m0 - m1), xs = base_s[r] + (is - s0 - s1);
+  const uint64_t c0 = b0 + 2u * lane;
+  if (s0 && xs < runs_cap) { runs[xs].src = c0 * chunk; runs[xs].dst = xm * chunk; }
+  if (s1 && xs + s0 < runs_cap) { runs[xs + s0].src = (c0 + 1) * chunk; runs[xs + s0].dst = (xm + m0) * chunk; }
+  if (e0 && xs + s0 - 1 < runs_cap) runs[xs + s0 - 1].len = min((c0 + 1) * chunk, total);
+  if (e1 && xs + s0 + s1 - 1 < runs_cap) runs[xs + s0 + s1 - 1].len = min((c0 + 2) * chunk, total);
+}
+
+__global__ __launch_bounds__(256) void tsg_gw_finish(GatherRun* __restrict__ runs, const uint64_t* __restrict__ tot_m,
+                                                     const uint64_t* __restrict__ tot_s, uint64_t runs_cap,
+                                                     const uint8_t* __restrict__ marks, uint64_t nchunks,
+                                                     uint32_t chunk, uint64_t total, uint64_t* __restrict__ meta) {
+  const uint64_t nruns = *tot_s;
+  const uint64_t tid = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x, step = static_cast<uint64_t>(gridDim.x) * 256;
+  if (nruns <= runs_cap)
+    for (uint64_t k = tid; k < nruns; k += step) runs[k].len -= runs[k].src;
+  if (tid == 0) {
+    // (the last chunk may be short; a run table that did not fit: a total no buffer holds, so the copy stores nothing)
+    uint64_t bytes = *tot_m * chunk;
+    if (nchunks && marks[nchunks - 1]) bytes -= nchunks * chunk - total;
+    meta[0] = nruns;
+    meta[1] = nruns <= runs_cap ? gather_round(bytes) : ~uint64_t(0);
+  }
+}
+
 }  // namespace
 
 bool gather_plan_launch(const void* cands, const uint32_t* ncands, uint32_t cand_cap, const uint32_t* fflags,
@@ -149,6 +367,83 @@ bool gather_plan_launch(const void* cands, const uint32_t* ncands, uint32_t cand
     e = hipGetLastError();
   }
   if (e != hipSuccess) { *err = std::string("gather launch: ") + hipGetErrorString(e); return false; }
+  return true;
+}
+
+namespace {
+size_t gw_align(size_t n) { return (n + 63) & ~size_t(63); }
+uint64_t gw_regions(uint64_t nchunks) { return (nchunks + kGwRegion - 1) / kGwRegion; }
+}  // namespace
+
+size_t gather_windows_scratch_bytes(uint64_t nchunks, uint32_t nfiles) {
+  const uint64_t nreg = gw_regions(nchunks);
+  return 128 + gw_align(nfiles) * 2 + gw_align(static_cast<size_t>(nfiles) * 4) + gw_align(nreg * 8) * 2 +
+         gw_align(nreg * 4) * 2 + (nreg + 1) * kGwRegion + 64;
+}
+
+GatherWindowScratch gather_windows_scratch_layout(void* scratch, uint64_t nchunks, uint32_t nfiles) {
+  const uint64_t nreg = gw_regions(nchunks);
+  uint8_t* sp = static_cast<uint8_t*>(scratch);
+  GatherWindowScratch sc;
+  sc.tot_m = reinterpret_cast<uint64_t*>(sp);
+  sc.pad_m = reinterpret_cast<uint64_t*>(sp + 16);
+  sc.tot_s = reinterpret_cast<uint64_t*>(sp + 64);
+  sc.pad_s = reinterpret_cast<uint64_t*>(sp + 80);
+  sp += 128;
+  sc.any = sp; sp += gw_align(nfiles);
+  sc.whole = sp; sp += gw_align(nfiles);
+  sc.cnt = reinterpret_cast<uint32_t*>(sp); sp += gw_align(static_cast<size_t>(nfiles) * 4);
+  sc.base_m = reinterpret_cast<uint64_t*>(sp); sp += gw_align(nreg * 8);
+  sc.base_s = reinterpret_cast<uint64_t*>(sp); sp += gw_align(nreg * 8);
+  sc.region_m = reinterpret_cast<uint32_t*>(sp); sp += gw_align(nreg * 4);
+  sc.region_s = reinterpret_cast<uint32_t*>(sp); sp += gw_align(nreg * 4);
+  sc.marks = sp;
+  return sc;
+}
+
+bool gather_windows_launch(const void* cands, const uint32_t* ncands, uint32_t cand_cap, const uint32_t* fflags,
+                           const uint64_t* offsets, uint32_t nfiles, uint32_t lead, bool all, const uint8_t* wrows,
+                           uint32_t nrows, uint32_t chunk, uint64_t total, const GatherWindowOpts& o,
+                           const GatherWindowScratch& sc, uint8_t* cls, GatherRun* runs, uint64_t runs_cap,
+                           uint64_t* meta, hipStream_t s, std::string* err) {
+  const uint64_t nchunks = (total + chunk - 1) / chunk, nreg64 = gw_regions(nchunks);
+  if (chunk == 0 || chunk % 128 != 0 || nreg64 > 0xffffffffull / kGwWaves) { *err = "gather windows: chunk grid out of range"; return false; }
+  const uint32_t nreg = static_cast<uint32_t>(nreg64);
+  hipError_t e = hipMemsetAsync(sc.tot_m, 0, gather_windows_scratch_bytes(nchunks, nfiles), s);
+  if (e == hipSuccess && nfiles) e = hipMemsetAsync(cls, 0, nfiles, s);
+  if (e != hipSuccess) { *err = std::string("gather windows: ") + hipGetErrorString(e); return false; }
+  // (grid-stride kernels: at most 1024 workgroups, as tsg_gather_mark's; the candidate passes cannot know the
+  // list's length on the host and take the capacity's grid)
+  auto grid = [](uint64_t n) { const uint64_t b = (n + 255) / 256; return dim3(static_cast<uint32_t>(b < 1 ? 1 : b > 1024 ? 1024 : b)); };
+  const uint4* cd = static_cast<const uint4*>(cands);
+  hipLaunchKernelGGL(tsg_gw_flags, grid(cand_cap), dim3(256), 0, s, cd, ncands, cand_cap, offsets, nfiles, lead, wrows,
+                     nrows, sc.any, sc.whole);
+  hipLaunchKernelGGL(tsg_gw_class, grid(nfiles), dim3(256), 0, s, offsets, nfiles, lead, fflags, all ? 1u : 0u,
+                     o.min_file, static_cast<const uint8_t*>(sc.any), static_cast<const uint8_t*>(sc.whole), cls,
+                     sc.marks, chunk, nchunks);
+  hipLaunchKernelGGL(tsg_gw_windows, grid(cand_cap), dim3(256), 0, s, cd, ncands, cand_cap, offsets, nfiles, lead,
+                     static_cast<const uint8_t*>(cls), sc.whole, sc.marks, chunk, nchunks, o.before, o.after);
+  hipLaunchKernelGGL(tsg_gw_count, grid(nchunks), dim3(256), 0, s, static_cast<const uint8_t*>(sc.marks), nchunks,
+                     offsets, nfiles, lead, static_cast<const uint8_t*>(cls), sc.cnt, chunk);
+  hipLaunchKernelGGL(tsg_gw_demote, grid(nfiles), dim3(256), 0, s, offsets, nfiles, lead, cls,
+                     static_cast<const uint8_t*>(sc.whole), static_cast<const uint32_t*>(sc.cnt), sc.marks, chunk,
+                     nchunks);
+  hipLaunchKernelGGL(tsg_gw_fill, grid(nchunks), dim3(256), 0, s, sc.marks, nchunks, offsets, nfiles, lead,
+                     static_cast<const uint8_t*>(cls), chunk);
+  if (nreg)
+    hipLaunchKernelGGL(tsg_gw_regions, dim3((nreg + 255u) / 256u), dim3(256), 0, s,
+                       static_cast<const uint8_t*>(sc.marks), nreg, sc.region_m, sc.region_s);
+  region_scan_launch(sc.region_m, nreg, sc.base_m, sc.tot_m, sc.pad_m, s);
+  region_scan_launch(sc.region_s, nreg, sc.base_s, sc.tot_s, sc.pad_s, s);
+  if (nreg)
+    hipLaunchKernelGGL(tsg_gw_runs, dim3((nreg + kGwWaves - 1) / kGwWaves), dim3(256), 0, s,
+                       static_cast<const uint8_t*>(sc.marks), nreg, static_cast<const uint64_t*>(sc.base_m),
+                       static_cast<const uint64_t*>(sc.base_s), runs, runs_cap, chunk, total);
+  hipLaunchKernelGGL(tsg_gw_finish, grid(runs_cap), dim3(256), 0, s, runs, static_cast<const uint64_t*>(sc.tot_m),
+                     static_cast<const uint64_t*>(sc.tot_s), runs_cap, static_cast<const uint8_t*>(sc.marks), nchunks,
+                     chunk, total, meta);
+  e = hipGetLastError();
+  if (e != hipSuccess) { *err = std::string("gather windows launch: ") + hipGetErrorString(e); return false; }
   return true;
 }
 

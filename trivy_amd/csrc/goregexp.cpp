@@ -103,6 +103,16 @@ int32_t rune_before(const uint8_t* s, size_t pos) {
   return c < 0x80 ? c : 0xFFFD;
 }
 
+// The furthest byte index a decode_rune at `pos` of s[0, len) asks for: the
+// rune's own bytes, or len when the text ends before the sequence the lead
+// byte announces is complete (the decode then depends on the text's end).
+size_t rune_reach(const uint8_t* s, size_t len, size_t pos) {
+  if (pos >= len) return len;
+  const uint8_t c = s[pos];
+  const size_t need = c < 0xC2 ? 1 : c < 0xE0 ? 2 : c < 0xF0 ? 3 : c <= 0xF4 ? 4 : 1;
+  return pos + need <= len ? pos + need - 1 : len;
+}
+
 // ------------------------------------------------------------------ parser
 struct Flags { bool i = false, m = false, s = false, U = false; };
 
@@ -827,7 +837,14 @@ class Machine {
     stack_.reserve(64);
   }
 
+  // kTrack: examined() is afterwards the furthest byte index the run asked
+  // for (len: it asked for the end of the text) -- Regexp::match_at_examined
+  template <bool kTrack = false>
   bool match(const uint8_t* s, size_t len, size_t pos0, bool anchored, Cap* caps_out) {
+    auto decode_rune = [&](const uint8_t* p, size_t n, int32_t* r, int* w) {
+      re::decode_rune(p, n, r, w);
+      if (kTrack) ex_ = std::max(ex_, rune_reach(s, len, static_cast<size_t>(p - s)));
+    };
     matched_ = false;
     std::fill(matchcap_.begin(), matchcap_.end(), -1);
     int rq = 0, nq = 1;
@@ -881,7 +898,12 @@ class Machine {
   // explored once, in priority order (the Pike VM's thread order), so the
   // first Match reached is the VM's match with the same submatches.
   // Returns 1 match, 0 none, -1 a thread ran past the window (caller: VM).
+  template <bool kTrack = false>
   int backtrack(const uint8_t* s, size_t len, size_t pos0, size_t window, Cap* caps_out) {
+    auto decode_rune = [&](const uint8_t* p, size_t n, int32_t* r, int* w) {
+      re::decode_rune(p, n, r, w);
+      if (kTrack) ex_ = std::max(ex_, rune_reach(s, len, static_cast<size_t>(p - s)));
+    };
     const size_t end = std::min(len, pos0 + window);
     const size_t npos = end - pos0 + 1;
     // visited (pc, pos) pairs: generation stamps in one per-thread array
@@ -961,6 +983,9 @@ class Machine {
     return 0;
   }
 
+  void reset_examined() { ex_ = 0; }
+  size_t examined() const { return ex_; }
+
  private:
   const Prog& p_;
   int ncap_;
@@ -970,6 +995,7 @@ class Machine {
   uint32_t size_[2];
   std::vector<Cap> matchcap_, scratch_;
   bool matched_ = false;
+  size_t ex_ = 0;
   uint8_t first_[256] = {0};
   struct Frame { uint32_t pc; int slot; Cap old; };
   std::vector<Frame> stack_;
@@ -1084,7 +1110,11 @@ class LazyDfa {
   }
 
   // -1: no match; -2: state budget exceeded (caller falls back to the VM)
-  long match_end(const uint8_t* s, size_t len, size_t pos) {
+  // kTrack: *ex = the furthest byte index the run asked for (len: the end of
+  // the text); a state whose only thread is Match ends the run without the
+  // next byte, which the transition would only read to find the same.
+  template <bool kTrack = false>
+  long match_end(const uint8_t* s, size_t len, size_t pos, size_t* ex = nullptr) {
     const int32_t pr = pos == 0 ? -1 : rune_before(s, pos);
     const uint8_t c0 = cat(pr);
     int st = start_[c0];                             // the start state per previous-rune category
@@ -1098,10 +1128,13 @@ class LazyDfa {
     size_t p = pos;
     for (;;) {
       if (st == 0) break;
+      if (kTrack && accept_only(st)) { end = static_cast<long>(p); break; }
       if (p >= len) {
+        if (kTrack) *ex = len;
         if (eot(st)) end = static_cast<long>(len);
         break;
       }
+      if (kTrack) *ex = std::max(*ex, rune_reach(s, len, p));
       int k, w;
       if (s[p] < 0x80) { k = ascii_cls_[s[p]]; w = 1; }
       else { int32_t r; decode_rune(s + p, len - p, &r, &w); k = class_of(r); }
@@ -1123,6 +1156,7 @@ class LazyDfa {
     uint8_t prev = 0;                // category of the previous rune
     std::vector<int32_t> next;       // per class: (state << 1) | match-before-this-rune; -1 unknown
     int8_t eot = -1;
+    int8_t accept_only = -1;
   };
   static constexpr size_t kMaxStates = 4096;
   int start_[4] = {-1, -1, -1, -1};
@@ -1228,6 +1262,23 @@ class LazyDfa {
     if (S.next.size() < cls_rep_.size()) S.next.resize(cls_rep_.size(), -1);
     S.next[k] = t;
     return t;
+  }
+
+  // the state's one seed reaches Match through Nop / Capture alone: whatever
+  // comes next, the run matches here and nothing lives on
+  bool accept_only(int st) {
+    State& S = states_[st];
+    if (S.accept_only < 0) {
+      bool a = S.seeds.size() == 1;
+      uint32_t pc = a ? S.seeds[0] : 0;
+      for (size_t hops = 0; a && p_.inst[pc].op != IOp::Match; ++hops) {
+        const IOp op = p_.inst[pc].op;
+        if ((op != IOp::Nop && op != IOp::Capture) || hops > p_.inst.size()) a = false;
+        else pc = p_.inst[pc].out;
+      }
+      S.accept_only = a ? 1 : 0;
+    }
+    return S.accept_only == 1;
   }
 
   bool eot(int st) {
@@ -1452,8 +1503,11 @@ std::unique_ptr<Regexp> Regexp::compile(const std::string& pattern, std::string*
   return re;
 }
 
-bool Regexp::match_at(const uint8_t* text, size_t len, size_t pos, bool anchored, int ncap_wanted,
-                      Cap* caps) const {
+// match_at and match_at_examined: one body, instantiated with and without
+// the examined position, so the plain calls pay nothing for it
+template <bool kTrack>
+static bool match_at_impl(const Prog& prog_, uint64_t id_, long max_width_, const uint8_t* text, size_t len, size_t pos,
+                          bool anchored, Cap* caps, size_t* examined) {
   if (prog_.start == 0) return false;
   // one Machine per (thread, Regexp): a direct-mapped per-thread cache keyed
   // by the Regexp's unique (sequential) id -- one probe per call, where a
@@ -1462,22 +1516,37 @@ bool Regexp::match_at(const uint8_t* text, size_t len, size_t pos, bool anchored
   constexpr size_t kSlots = 4096;
   thread_local std::vector<std::pair<uint64_t, std::unique_ptr<Machine>>> cache(kSlots);
   auto& slot = cache[id_ & (kSlots - 1)];
-  (void)ncap_wanted;
   if (slot.first != id_ || !slot.second) {
     slot.second.reset(new Machine(prog_, 2 * (prog_.num_cap + 1)));
     slot.first = id_;
   }
+  Machine& m = *slot.second;
+  if (kTrack) m.reset_examined();
   // TSG_RE_NO_BACKTRACK=1: the Pike VM only (differential tests)
   static const bool no_bt = std::getenv("TSG_RE_NO_BACKTRACK") && std::atoi(std::getenv("TSG_RE_NO_BACKTRACK")) != 0;
+  bool done = false, res = false;
   if (!no_bt && anchored && max_width_ >= 0 && pos <= len) {
     // Go's bit-state limit: (program size) x (window + 1) <= 256 Kbit
     const size_t window = std::min<size_t>(static_cast<size_t>(max_width_), len - pos);
     if (prog_.inst.size() * (window + 1) <= 256 * 1024) {
-      const int r = slot.second->backtrack(text, len, pos, window, caps);
-      if (r >= 0) return r == 1;
+      const int r = m.template backtrack<kTrack>(text, len, pos, window, caps);
+      if (r >= 0) { done = true; res = r == 1; }
     }
   }
-  return slot.second->match(text, len, pos, anchored, caps);
+  if (!done) res = m.template match<kTrack>(text, len, pos, anchored, caps);
+  if (kTrack) *examined = m.examined();
+  return res;
+}
+
+bool Regexp::match_at(const uint8_t* text, size_t len, size_t pos, bool anchored, int ncap_wanted,
+                      Cap* caps) const {
+  (void)ncap_wanted;
+  return match_at_impl<false>(prog_, id_, max_width_, text, len, pos, anchored, caps, nullptr);
+}
+
+bool Regexp::match_at_examined(const uint8_t* text, size_t len, size_t pos, Cap* caps, size_t* examined) const {
+  *examined = 0;
+  return match_at_impl<true>(prog_, id_, max_width_, text, len, pos, true, caps, examined);
 }
 
 long Regexp::match_end(const uint8_t* text, size_t len, size_t pos) const {
@@ -1534,6 +1603,52 @@ long Regexp::match_end_dfa(const uint8_t* text, size_t len, size_t pos) const {
     slot.second.reset(new LazyDfa(prog_));
     std::vector<Cap> caps(2 * (prog_.num_cap + 1));
     e = match_at(text, len, pos, true, 0, caps.data()) ? caps[1] : -1;
+  }
+  return e;
+}
+
+long Regexp::match_end_examined(const uint8_t* text, size_t len, size_t pos, size_t* examined) const {
+  *examined = 0;
+  if (prog_.start == 0) return -1;
+  if (pos > len) { *examined = len; return -1; }
+  const size_t nslots = 2 * (static_cast<size_t>(prog_.num_cap) + 1);
+  if (!span_shape_ && max_width_ >= 0 &&
+      prog_.inst.size() * (std::min<size_t>(static_cast<size_t>(max_width_), len - pos) + 1) <= 256 * 1024) {
+    thread_local std::vector<Cap> bcaps;
+    bcaps.resize(nslots);
+    return match_at_examined(text, len, pos, bcaps.data(), examined) ? bcaps[1] : -1;
+  }
+  if (span_shape_) {
+    // (as match_end_dfa's span path; a greedy star searches to the end of the text)
+    const size_t n1 = span_l1_.size(), n2 = span_l2_.size();
+    if (pos + n1 + n2 > len) { *examined = len; return -1; }
+    *examined = pos + n1 - (n1 ? 1 : 0);
+    if (std::memcmp(text + pos, span_l1_.data(), n1) != 0) return -1;
+    if (span_shape_ == 2) {
+      const void* q = memmem(text + pos + n1, len - pos - n1, span_l2_.data(), n2);
+      if (!q) { *examined = len; return -1; }
+      const long e = static_cast<long>(static_cast<const uint8_t*>(q) - text + n2);
+      *examined = static_cast<size_t>(e) - 1;
+      return e;
+    }
+    *examined = len;
+    return match_end_dfa(text, len, pos);
+  }
+  // a DFA of this call's own thread cache entry would be shared with
+  // match_end_dfa's; the tracked runs are few (windowed files only), so they
+  // keep a cache of their own
+  constexpr size_t kSlots = 4096;
+  thread_local std::vector<std::pair<uint64_t, std::unique_ptr<LazyDfa>>> cache(kSlots);
+  auto& slot = cache[id_ & (kSlots - 1)];
+  if (slot.first != id_ || !slot.second) {
+    slot.second.reset(new LazyDfa(prog_));
+    slot.first = id_;
+  }
+  long e = slot.second->match_end<true>(text, len, pos, examined);
+  if (e == -2) {
+    slot.second.reset(new LazyDfa(prog_));
+    std::vector<Cap> caps(nslots);
+    e = match_at_examined(text, len, pos, caps.data(), examined) ? caps[1] : -1;
   }
   return e;
 }

@@ -134,6 +134,17 @@ class Regexp {
   // match_end's lazy-DFA path alone (bounded-width patterns otherwise take
   // the backtracker): the same result, for tests
   long match_end_dfa(const uint8_t* text, size_t len, size_t pos) const;
+  // match_at(.., anchored = true, ..) and match_end that also give the
+  // furthest byte index of the text the run asked for -- a byte's value, the
+  // lookahead of a rune decode, of \b and of $ included; len when it asked
+  // for the end of the text.  The result on a longer text with the same first
+  // len bytes is the same whenever *examined < len: this is how a run on a
+  // gathered window (a cut text) is known to equal the run on the whole file.
+  // (The Pike VM decodes one rune ahead of the one it steps on, so a run that
+  // takes it reports up to two runes past what it strictly needed; the
+  // backtracker and the lazy DFA report exactly.)
+  bool match_at_examined(const uint8_t* text, size_t len, size_t pos, Cap* caps, size_t* examined) const;
+  long match_end_examined(const uint8_t* text, size_t len, size_t pos, size_t* examined) const;
   // Regexp.MatchString (with a gate set: false without running the VM when
   // no gate literal occurs in the text -- no match can exist then)
   bool match_string(const uint8_t* text, size_t len) const;

@@ -716,7 +716,9 @@ StrRef put(std::string* arena, const std::string& v) {
 }
 
 // scanner.go:475-558 on the (virtual) censored buffer; appends to `out`.
-void to_finding(const Rule& rule, Loc loc, const CensoredView& cv, SecretBuilder* out) {
+// (View: CensoredView, or WindowView over a file gathered in windows)
+template <class View>
+void to_finding(const Rule& rule, Loc loc, const View& cv, SecretBuilder* out) {
   FindingRec f;
   f.rule = &rule;
   const size_t n = cv.size();
@@ -896,6 +898,19 @@ Secret scan_file(const Ruleset& rs, std::string path, const uint8_t* content, si
   return scan_file(rs, path.data(), path.size(), content, len, binary, plan, nl);
 }
 
+namespace {
+// scanner.go:446-453: the findings sorted by (RuleID, Match), into one block
+Secret sorted_secret(SecretBuilder& out) {
+  auto& fs = out.findings;
+  const std::string& ar = out.arena;
+  GoSort<FindingRec>(&fs, [&fs, &ar](size_t i, size_t j) {
+    if (fs[i].rule->id != fs[j].rule->id) return fs[i].rule->id < fs[j].rule->id;
+    return ar.compare(fs[i].match.off, fs[i].match.len, ar, fs[j].match.off, fs[j].match.len) < 0;
+  }).run();
+  return Secret::build(out);
+}
+}  // namespace
+
 // (the path by pointer and length: it is copied into the per-thread builder,
 // whose buffer is reused from file to file -- the engine's confirm pool made a
 // std::string of every confirmed file's path, a heap allocation and a free per
@@ -989,15 +1004,287 @@ Secret scan_file(const Ruleset& rs, const char* path_p, size_t path_n, const uin
     }
   }
   pc.lap(3);
-  auto& fs = out.findings;
-  const std::string& ar = out.arena;
-  GoSort<FindingRec>(&fs, [&fs, &ar](size_t i, size_t j) {
-    if (fs[i].rule->id != fs[j].rule->id) return fs[i].rule->id < fs[j].rule->id;
-    return ar.compare(fs[i].match.off, fs[i].match.len, ar, fs[j].match.off, fs[j].match.len) < 0;
-  }).run();
-  Secret res = Secret::build(out);
+  Secret res = sorted_secret(out);
   pc.lap(4);
   return res;
+}
+
+// ------------------------------------------------- a file gathered in windows
+namespace {
+
+// The run of wf holding file byte x, or NULL.
+const WindowRun* run_of(const WindowFile& wf, uint64_t x) {
+  size_t lo = 0, hi = wf.nruns;
+  while (lo < hi) {
+    const size_t mid = (lo + hi) / 2;
+    if (wf.runs[mid].a <= x) lo = mid + 1; else hi = mid;
+  }
+  if (lo == 0) return nullptr;
+  const WindowRun* r = wf.runs + (lo - 1);
+  return x < r->b ? r : nullptr;
+}
+// ... holding [x, y), y > x
+const WindowRun* run_of(const WindowFile& wf, uint64_t x, uint64_t y) {
+  const WindowRun* r = run_of(wf, x);
+  return r && y <= r->b ? r : nullptr;
+}
+
+// CensoredView's interface over the gathered runs of one file.  A read that
+// would leave them on a side that is not the file's own start or end sets
+// bad(): the file's result is then dropped and the file fetched whole.
+class WindowView {
+ public:
+  WindowView(const WindowFile& wf, std::vector<Loc>& spans, std::vector<uint64_t>& scratch)
+      : wf_(wf), n_(wf.len), iv_(spans), local_(scratch) {
+    std::sort(spans.begin(), spans.end(), [](const Loc& a, const Loc& b) { return a.start < b.start; });
+    size_t m = 0;
+    for (size_t i = 0; i < spans.size(); ++i) {
+      const Loc l = spans[i];
+      if (l.end <= l.start) continue;
+      if (m > 0 && l.start <= spans[m - 1].end) spans[m - 1].end = std::max(spans[m - 1].end, l.end);
+      else spans[m++] = l;
+    }
+    spans.resize(m);
+    first_ = wf.file_off / wf.chunk;
+    local_.assign(1, 0);
+  }
+  bool bad() const { return bad_; }
+  size_t size() const { return n_; }
+  bool censored(long i) const {
+    auto it = std::upper_bound(iv_.begin(), iv_.end(), i, [](long v, const Loc& l) { return v < l.start; });
+    if (it == iv_.begin()) return false;
+    --it;
+    return i < it->end;
+  }
+  uint64_t count_nl(size_t a, size_t b) const {
+    if (b <= a) return 0;
+    uint64_t n = orig_nl(a, b);
+    for (auto it = first_ending_after(a); it != iv_.end() && static_cast<size_t>(it->start) < b; ++it) {
+      size_t x = std::max<size_t>(a, it->start), y = std::min<size_t>(b, it->end);
+      if (x < y) n -= orig_nl(x, y);
+    }
+    return n;
+  }
+  long prev_nl(size_t pos) const {
+    if (pos == 0) return -1;
+    const WindowRun* r = run_of(wf_, pos - 1);
+    if (!r) { bad_ = true; return -1; }
+    long i = static_cast<long>(pos) - 1;
+    const long a = static_cast<long>(r->a);
+    while (i >= a) {
+      const void* q = memrchr(r->p, '\n', static_cast<size_t>(i - a) + 1);
+      if (!q) break;
+      const long k = a + (static_cast<const uint8_t*>(q) - r->p);
+      if (!censored(k)) return k;
+      auto it = std::upper_bound(iv_.begin(), iv_.end(), k, [](long v, const Loc& l) { return v < l.start; });
+      --it;
+      i = it->start - 1;
+    }
+    // (a censored span is a match, and a match lies inside one run: i >= a - 1)
+    if (a != 0) bad_ = true;
+    return -1;
+  }
+  size_t next_nl(size_t pos) const {
+    if (pos >= n_) return n_;
+    const WindowRun* r = run_of(wf_, pos);
+    if (!r) { bad_ = true; return n_; }
+    size_t i = pos;
+    while (i < r->b) {
+      const void* q = memchr(r->p + (i - r->a), '\n', r->b - i);
+      if (!q) break;
+      const size_t k = r->a + (static_cast<const uint8_t*>(q) - r->p);
+      if (!censored(static_cast<long>(k))) return k;
+      auto it = std::upper_bound(iv_.begin(), iv_.end(), static_cast<long>(k), [](long v, const Loc& l) { return v < l.start; });
+      --it;
+      i = static_cast<size_t>(it->end);
+    }
+    if (r->b != n_) bad_ = true;
+    return n_;
+  }
+  StrRef put(std::string* arena, size_t a, size_t b) const {
+    StrRef ref{static_cast<uint32_t>(arena->size()), static_cast<uint32_t>(b - a)};
+    if (b <= a) { ref.len = 0; return ref; }
+    const WindowRun* r = run_of(wf_, a, b);
+    if (!r) { bad_ = true; ref.len = 0; return ref; }
+    arena->append(reinterpret_cast<const char*>(r->p) + (a - r->a), b - a);
+    char* d = &(*arena)[ref.off];
+    for (auto it = first_ending_after(a); it != iv_.end() && static_cast<size_t>(it->start) < b; ++it) {
+      size_t x = std::max<size_t>(a, it->start), y = std::min<size_t>(b, it->end);
+      for (size_t k = x; k < y; ++k) d[k - a] = '*';
+    }
+    return ref;
+  }
+
+ private:
+  const WindowFile& wf_;
+  size_t n_;
+  const std::vector<Loc>& iv_;
+  std::vector<uint64_t>& local_;           // local_[k] = '\n' in the chunks [first_, first_ + k) (K1's counts)
+  uint64_t first_ = 0;
+  mutable bool bad_ = false;
+
+  std::vector<Loc>::const_iterator first_ending_after(size_t a) const {
+    return std::upper_bound(iv_.begin(), iv_.end(), static_cast<long>(a), [](long v, const Loc& l) { return v < l.end; });
+  }
+  // '\n' in the frame's bytes [first_ * chunk, off + x): whole chunks from
+  // K1's table, the partial chunk from its gathered bytes (the head chunk's
+  // lie in front of run 0, which starts on that chunk's boundary)
+  uint64_t prefix_at(uint64_t x) const {
+    const uint64_t ch = wf_.chunk, g = wf_.file_off + x, k = g / ch;
+    while (local_.size() <= k - first_) {
+      const uint64_t j = first_ + local_.size() - 1;
+      local_.push_back(local_.back() + wf_.chunk_nl[j]);
+    }
+    const uint64_t part = g - k * ch;
+    if (part == 0) return local_[k - first_];
+    if (k * ch < wf_.file_off) {            // the head chunk
+      const uint64_t head = wf_.file_off - k * ch;
+      if (wf_.nruns == 0 || wf_.runs[0].a != 0 || x > wf_.runs[0].b) { bad_ = true; return 0; }
+      return local_[k - first_] + count_newlines(wf_.runs[0].p - head, part);
+    }
+    const uint64_t a = k * ch - wf_.file_off;
+    const WindowRun* r = run_of(wf_, a, x);
+    if (!r) { bad_ = true; return 0; }
+    return local_[k - first_] + count_newlines(r->p + (a - r->a), part);
+  }
+  uint64_t orig_nl(size_t a, size_t b) const {
+    const WindowRun* r = run_of(wf_, a, b);
+    if (r && b - a <= 2 * static_cast<size_t>(wf_.chunk)) return count_newlines(r->p + (a - r->a), b - a);
+    const uint64_t hi = prefix_at(b), lo = prefix_at(a);
+    return bad_ ? 0 : hi - lo;
+  }
+};
+
+// find_all_from_candidates over the runs: every anchored run is made on the
+// run that holds its start, as a text cut at the run's end.  false: a run
+// asked for bytes that were not gathered (see scan_file_windows).
+bool find_all_windows(const re::Regexp& re, const WindowFile& wf, const std::vector<uint64_t>& starts, bool submatch,
+                      std::vector<re::Cap>* out) {
+  const int ncap = 2 * (re.num_subexp() + 1);
+  thread_local std::vector<re::Cap> caps;
+  caps.resize(ncap);
+  const size_t len = wf.len;
+  size_t pos = 0;
+  long prev_end = -1;
+  size_t idx = 0;
+  while (pos <= len) {
+    bool found = false;
+    while (idx < starts.size()) {
+      const size_t s = starts[idx];
+      if (s < pos) { ++idx; continue; }
+      if (s >= len) return false;                      // (such a start makes the file whole on the device)
+      const WindowRun* r = run_of(wf, s);
+      if (!r) return false;
+      // chain_boundary and \b look at up to 4 bytes in front of s and 3 behind it
+      if (r->a != 0 && s - r->a < 4) return false;
+      if (r->b != len && r->b - s < 4) return false;
+      const size_t llen = r->b - r->a, ls = s - r->a, lpos = pos > r->a ? pos - r->a : 0;
+      if (chain_boundary(r->p, llen, lpos, ls)) {
+        size_t ex = 0;
+        bool hit;
+        if (submatch) {
+          hit = re.match_at_examined(r->p, llen, ls, caps.data(), &ex);
+          if (hit) for (int k = 0; k < ncap; ++k) if (caps[k] >= 0) caps[k] += static_cast<re::Cap>(r->a);
+        } else {
+          const long e = re.match_end_examined(r->p, llen, ls, &ex);
+          hit = e >= 0;
+          if (hit) { caps[0] = static_cast<re::Cap>(s); caps[1] = static_cast<re::Cap>(r->a + e); }
+        }
+        if (ex >= llen && r->b != len) return false;  // the run asked for a byte past the window
+        if (hit) { found = true; break; }
+      }
+      ++idx;
+    }
+    if (!found) break;
+    bool accept = true;
+    if (static_cast<size_t>(caps[1]) == pos) {
+      if (caps[0] == prev_end) accept = false;
+      const WindowRun* r = run_of(wf, pos);
+      if (pos < len && !r) return false;
+      int32_t rn; int w = 0;
+      if (r) re::decode_rune(r->p + (pos - r->a), r->b - pos, &rn, &w);
+      if (r && r->b != len && r->b - pos < 4) return false;
+      pos = w > 0 ? pos + w : len + 1;
+    } else {
+      pos = static_cast<size_t>(caps[1]);
+    }
+    prev_end = caps[1];
+    if (accept) {
+      if (submatch) out->insert(out->end(), caps.begin(), caps.end());
+      else { out->push_back(caps[0]); out->push_back(caps[1]); }
+    }
+  }
+  return true;
+}
+
+}  // namespace
+
+Secret scan_file_windows(const Ruleset& rs, const char* path_p, size_t path_n, const WindowFile& wf, bool binary,
+                         const FilePlan& plan, bool* insufficient) {
+  *insufficient = false;
+  if (global_allow_path(rs, reinterpret_cast<const uint8_t*>(path_p), path_n)) return Secret::path_only(path_p, path_n);
+  thread_local SecretBuilder out_tl;
+  SecretBuilder& out = out_tl;
+  out.clear();
+  out.file_path.assign(path_p, path_n);
+  const std::string& path = out.file_path;
+  thread_local std::vector<Matched> matched_tl;
+  thread_local std::vector<Loc> spans_tl;
+  thread_local std::vector<uint64_t> nl_tl;
+  thread_local std::vector<re::Cap> m;
+  std::vector<Matched>& matched = matched_tl;
+  matched.clear();
+  // only rules confirmed from their candidates alone can be decided from
+  // windows: any other kind (the device makes such a file whole) is refused
+  for (size_t k = 0; k < plan.kind.size(); ++k)
+    if (plan.kind[k] != kPlanSkip && plan.kind[k] != kPlanNoMatch && (plan.kind[k] != kPlanCandidates || k >= rs.rules.size())) {
+      *insufficient = true;
+      return Secret();
+    }
+  for (const RuleCandidates& rc : plan.cands) {
+    if (rc.rule >= rs.rules.size() || plan.kind[rc.rule] != kPlanCandidates) continue;
+    const Rule& rule = rs.rules[rc.rule];
+    if (!rule.regex) continue;
+    if (rule.path && !rule.path->match_string(reinterpret_cast<const uint8_t*>(path.data()), path.size())) continue;
+    if (allow_path(rule.allow_rules, path)) continue;
+    const bool sub = !rule.secret_group_name.empty();
+    m.clear();
+    if (!find_all_windows(*rule.regex, wf, rc.starts, sub, &m)) { *insufficient = true; return Secret(); }
+    const size_t stride = sub ? 2 * (rule.regex->num_subexp() + 1) : 2;
+    for (size_t k = 0; k + stride <= m.size(); k += stride) {
+      const long s = m[k], e = m[k + 1];
+      const WindowRun* r = run_of(wf, static_cast<uint64_t>(s), static_cast<uint64_t>(std::max(e, s + 1)));
+      if (!r && e > s) { *insufficient = true; return Secret(); }
+      const uint8_t* mp = r ? r->p + (s - r->a) : reinterpret_cast<const uint8_t*>("");
+      if (global_allow_match(rs, mp, e - s) || allow_match(rule.allow_rules, mp, e - s)) continue;
+      if (!sub) { matched.push_back({&rule, {s, e}}); continue; }
+      for (int gi : rule.secret_groups) {
+        Loc l{m[k + 2 * gi], m[k + 2 * gi + 1]};
+        if (l.start < 0) { out.error = 1; continue; }   // (scan_file: flagged and skipped)
+        matched.push_back({&rule, l});
+      }
+    }
+  }
+  if (matched.empty()) {
+    Secret empty;
+    empty.error = out.error;
+    return empty;
+  }
+  std::vector<Loc>& spans = spans_tl;
+  spans.clear();
+  for (const auto& mt : matched) spans.push_back(mt.loc);
+  WindowView cv(wf, spans, nl_tl);
+  for (const auto& mt : matched) {
+    to_finding(*mt.rule, mt.loc, cv, &out);
+    if (cv.bad()) { *insufficient = true; return Secret(); }
+    if (binary) {
+      FindingRec& f = out.findings.back();
+      out.lines.resize(f.line_begin);
+      f.line_count = 0;
+      f.match = put(&out.arena, "Binary file " + go_quote(path) + " matches a rule " + go_quote(mt.rule->title));
+    }
+  }
+  return sorted_secret(out);
 }
 
 Secret Secret::build(const SecretBuilder& b) {

@@ -279,6 +279,33 @@ Secret scan_file(const Ruleset& rs, std::string path, const uint8_t* content, si
 Secret scan_file(const Ruleset& rs, const char* path, size_t path_len, const uint8_t* content, size_t len,
                  bool binary, const FilePlan* plan, const NlSource* nl = nullptr);
 
+// A file of which only windows were gathered (the device-only scan with
+// tsg_device_scan_opts; gather.h plan_gather_windows): file bytes [a, b) of
+// run k are at p[0, b - a).  The runs are sorted and disjoint, every a is a
+// K1 chunk boundary of the segment's frame or 0, and run 0 starts at file
+// byte 0 with the bytes between the chunk boundary below the file and the
+// file in front of p (the head).
+struct WindowRun { uint64_t a, b; const uint8_t* p; };
+struct WindowFile {
+  const WindowRun* runs = nullptr;
+  size_t nruns = 0;
+  size_t len = 0;                     // the file's length
+  const uint16_t* chunk_nl = nullptr; // K1's '\n' per chunk of the frame
+  uint32_t chunk = 0;
+  uint64_t file_off = 0;              // the file's offset in the frame
+};
+
+// scan_file for such a file.  Every active rule of the plan must be
+// kPlanCandidates (the only kind a windowed file has).  *insufficient: some
+// read would have left the gathered bytes on a side that is not the file's
+// own start or end -- an anchored regex run that examined a byte at or past
+// its run's end (Regexp::match_*_examined), a candidate with fewer than 4
+// gathered bytes in front, a line search that met a run's edge before its
+// '\n', a newline count over a partial chunk that was not gathered.  The
+// result is then empty and the caller confirms the file from all its bytes.
+Secret scan_file_windows(const Ruleset& rs, const char* path, size_t path_len, const WindowFile& wf, bool binary,
+                         const FilePlan& plan, bool* insufficient);
+
 // Exact Go FindAll(Submatch)Index restricted to candidate start offsets.
 // `starts` must be a sorted superset of every position where an anchored
 // match can start; the result equals re.find_all(text).

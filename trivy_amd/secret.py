@@ -375,7 +375,7 @@ class Scanner:
         return out + ({"ms": ms, "rounds": rounds},) if with_stats else out
 
     def ScanLayersGzipDevice(self, blobs, skip_files=(), skip_dirs=(), file_patterns=(), config_path="",
-                             with_stats=False, contents=False):
+                             with_stats=False, contents=False, window=None):
         """The layers of an image as the registry or `docker save` hands them
         over -- one gzip stream each -- scanned with only the compressed bytes
         and the confirmer's gather crossing the link:
@@ -393,11 +393,11 @@ class Scanner:
         ("unexpected EOF", "gzip: invalid checksum", ...); a malformed tar
         raises WalkError as PrepareLayerTarDevice does.  with_stats appends
         {"gz_bytes", "tar_bytes", "inflate_ms", "inflate_rounds"} to the list's
-        tuple: (layers, stats)."""
+        tuple: (layers, stats).  window: ScanBatchDevice's, for every layer's scan."""
         views = self._blob_views(blobs)
         opts = dict(skip_files=skip_files, skip_dirs=skip_dirs, file_patterns=file_patterns, config_path=config_path)
         slots, st = self._gzip_layer_slots(views, list(range(len(views))))
-        layers = [self._scan_layer_slot(d_tar, k, opts, contents) for d_tar, k in slots]
+        layers = [self._scan_layer_slot(d_tar, k, opts, contents, window) for d_tar, k in slots]
         if with_stats:
             return layers, {"gz_bytes": st["gz_bytes"], "tar_bytes": sum(k for _, k in slots), "inflate_ms": st["ms"],
                             "inflate_rounds": st["rounds"]}
@@ -444,10 +444,10 @@ class Scanner:
         slots = [(dst[int(do[k]):int(do[k + 1])], int(out_lens[k])) for k in range(len(idx))]
         return slots, {"gz_bytes": int(go[-1]), "ms": ist["ms"], "rounds": ist["rounds"]}
 
-    def _scan_layer_slot(self, d_tar, k, opts, contents):
+    def _scan_layer_slot(self, d_tar, k, opts, contents, window=None):
         """PrepareLayerTarDevice -> ScanBatchDevice on a tar of k bytes in HBM: (ScanArgs list, walk dict, [types.Secret])"""
         p_dst, offs, scan_paths, binf, walk, _ms = self.PrepareLayerTarDevice(d_tar, k, **opts)
-        secrets = self.ScanBatchDevice(p_dst, offs, scan_paths, binf)
+        secrets = self.ScanBatchDevice(p_dst, offs, scan_paths, binf, window=window)
         data = p_dst[:int(offs[-1])].cpu().numpy().tobytes() if contents and len(scan_paths) else None
         args = [ScanArgs(p, data[int(offs[j]):int(offs[j + 1])] if data is not None else (b"" if contents else None),
                          bool(binf[j])) for j, p in enumerate(scan_paths)]
@@ -543,7 +543,7 @@ class Scanner:
         return int(_lib.lib().tsg_layer_compression(v.ctypes.data if len(v) else None, len(v)))
 
     def ScanLayersCompressedDevice(self, blobs, skip_files=(), skip_dirs=(), file_patterns=(), config_path="",
-                                   with_stats=False, contents=False):
+                                   with_stats=False, contents=False, window=None):
         """ScanLayersGzipDevice for layers as layer.Uncompressed() takes them:
         each blob is a gzip stream, a zstd stream or a plain tar, told apart by
         its first bytes (tsg_layer_compression) as go-containerregistry's peek
@@ -557,7 +557,8 @@ class Scanner:
         Arguments and the per-layer result are ScanLayersGzipDevice's.  A
         stream that fails raises WalkError with its blob index and the status
         text.  with_stats appends {"gz_bytes", "zstd_bytes", "plain_bytes",
-        "tar_bytes", "inflate_ms", "zstd_ms", "inflate_rounds"}."""
+        "tar_bytes", "inflate_ms", "zstd_ms", "inflate_rounds"}.  window:
+        ScanBatchDevice's, for every layer's scan."""
         L = _lib.lib()
         views = self._blob_views(blobs)
         kinds = [int(L.tsg_layer_compression(v.ctypes.data, min(len(v), 4))) if len(v) else _lib.LAYER_NONE for v in views]
@@ -590,7 +591,7 @@ class Scanner:
             for k, i in enumerate(plain):
                 slots[i] = (d_p[int(po[k]):int(po[k + 1]) + (16 if k == len(plain) - 1 else 0)], len(views[i]))
                 stats["plain_bytes"] += len(views[i])
-        layers = [self._scan_layer_slot(d_tar, k, opts, contents) for d_tar, k in slots]
+        layers = [self._scan_layer_slot(d_tar, k, opts, contents, window) for d_tar, k in slots]
         stats["tar_bytes"] = sum(k for _, k in slots)
         return (layers, stats) if with_stats else layers
 
@@ -632,7 +633,7 @@ class Scanner:
             s.pop("Error", None)
         return (out, stats) if with_stats else out
 
-    def _scan_device_tensor(self, d_data, offsets, paths, binary, h_data, with_stats):
+    def _scan_device_tensor(self, d_data, offsets, paths, binary, h_data, with_stats, window=None):
         """tsg_scan_batch_device (h_data None) or tsg_scan_batch_resident on a
         uint8 device tensor; returns (findings, stats or None, C result)."""
         import torch
@@ -650,7 +651,12 @@ class Scanner:
         b = np.ascontiguousarray(binary if binary is not None else np.zeros(max(nfiles, 1)), dtype=np.uint8)
         torch.cuda.current_stream(d_data.device).synchronize()     # the engine runs on its own streams
         res = ctypes.c_void_p()
-        if h_data is None:
+        if h_data is None and window is not None:
+            opts = _lib.scan_opts(window)
+            _lib.check(L.tsg_scan_batch_device_opts(self.engine(), ctypes.c_void_p(d_data.data_ptr()), off.ctypes.data,
+                                                    nfiles, cpaths, lens, b.ctypes.data, ctypes.byref(opts),
+                                                    ctypes.byref(res)))
+        elif h_data is None:
             _lib.check(L.tsg_scan_batch_device(self.engine(), ctypes.c_void_p(d_data.data_ptr()), off.ctypes.data,
                                                nfiles, cpaths, lens, b.ctypes.data, ctypes.byref(res)))
         else:
@@ -666,13 +672,14 @@ class Scanner:
             if with_stats:
                 stats = _lib.result_stats(res)
                 stats.update(_lib.result_gather_stats(res))
+                stats.update(_lib.result_gather_window_stats(res))
         finally:
             L.tsg_result_free(res)
         for s in out:
             s.pop("Error", None)
         return (out, stats) if with_stats else out
 
-    def ScanBatchDevice(self, d_data, offsets, paths, binary=None, with_stats=False):
+    def ScanBatchDevice(self, d_data, offsets, paths, binary=None, with_stats=False, window=None):
         """The device-only scan (tsg_scan_batch_device): the batch exists only
         in HBM.  d_data: uint8 device tensor, the files packed back to back,
         16-byte aligned, with at least 16 bytes after the batch; offsets:
@@ -682,6 +689,17 @@ class Scanner:
         else of the batch crosses the link.  The caller's stream is
         synchronised first.  with_stats adds the scan's stats and the gather's
         (gather_files, gather_bytes, gather_runs, gather_ms, gather_retries).
+
+        window = (before, after, min_file) (tsg_scan_batch_device_opts): files
+        of at least min_file bytes whose candidates the confirmer decides from
+        their starts alone contribute only the bytes [s - before, s + after)
+        around each candidate start s (and their first chunk), not the whole
+        file; a file whose confirmation would read past what was gathered is
+        fetched whole at the end of the call.  The findings are the same for
+        every setting.  with_stats then also holds window_files, window_runs,
+        window_bytes, fallback_files and fallback_bytes
+        (tsg_result_gather_window_stats); gather_bytes counts everything that
+        crossed.  None, or before = after = 0: whole files.
 
         The chain for files uploaded as read, of any kind (CRLF text, binaries
         to drop, binary .pyc files), is PrepareBatchDevice -> ScanBatchDevice,
@@ -696,7 +714,7 @@ class Scanner:
 
             dst, new_off, total, _ = sc.StripCR(d_raw, d_raw_offsets, nfiles, raw_total)
             found = sc.ScanBatchDevice(dst, new_off.cpu().numpy(), paths)"""
-        return self._scan_device_tensor(d_data, offsets, paths, binary, None, with_stats)
+        return self._scan_device_tensor(d_data, offsets, paths, binary, None, with_stats, window)
 
     def ScanBatchResident(self, d_data, h_data, offsets, paths, binary=None, with_stats=False):
         """tsg_scan_batch_resident: as ScanBatchDevice, with the caller's host
@@ -1330,6 +1348,92 @@ def plan_gather(offsets, need, chunk, lead=0):
     return goff[:nfiles], runs[:nruns.value].copy(), total.value
 
 
+def plan_gather_windows(offsets, cands, fflags, all_rules, windowable, chunk, window, lead=0):
+    """The windowed gather layout (tsg_test_plan_gather_windows, csrc/gather.h
+    plan_gather_windows): cands = [(file, rule, start)]; returns a dict of cls,
+    first_run, marks, runs [nruns, 3], total.  Tests only."""
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    nfiles = len(off) - 1
+    cf = np.array([c[0] for c in cands] or [0], np.uint32)
+    cr = np.array([c[1] for c in cands] or [0], np.uint32)
+    cs = np.array([c[2] for c in cands] or [0], np.uint64)
+    ff = np.ascontiguousarray(fflags if len(fflags) else [0], dtype=np.uint32)
+    wr = np.ascontiguousarray(windowable if len(windowable) else [0], dtype=np.uint8)
+    nchunks = (int(off[-1]) + chunk - 1) // chunk if nfiles else 0
+    cls = np.zeros(max(nfiles, 1), np.uint8)
+    first = np.zeros(max(nfiles, 1), np.uint32)
+    marks = np.zeros(max(nchunks, 1), np.uint8)
+    runs = np.zeros((nchunks // 2 + 2, 3), np.uint64)
+    nruns, total = ctypes.c_size_t(), ctypes.c_uint64()
+    opts = _lib.scan_opts(window)
+    _lib.check(_lib.lib().tsg_test_plan_gather_windows(
+        off.ctypes.data, nfiles, lead, cf.ctypes.data, cr.ctypes.data, cs.ctypes.data, len(cands), ff.ctypes.data,
+        1 if all_rules else 0, wr.ctypes.data, len(windowable), chunk, ctypes.byref(opts), cls.ctypes.data,
+        first.ctypes.data, marks.ctypes.data, runs.ctypes.data, len(runs), ctypes.byref(nruns), ctypes.byref(total)))
+    return {"cls": cls[:nfiles], "first_run": first[:nfiles], "marks": marks[:nchunks],
+            "runs": runs[:nruns.value].copy(), "total": total.value}
+
+
+def windowable_rows(scanner):
+    """(one byte per row of the rule table, number of rules) (tsg_test_windowable_rows).  Tests only."""
+    n, nr = ctypes.c_size_t(), ctypes.c_size_t()
+    _lib.check(_lib.lib().tsg_test_windowable_rows(scanner._rs, None, 0, ctypes.byref(n), ctypes.byref(nr)))
+    rows = np.zeros(max(n.value, 1), np.uint8)
+    _lib.check(_lib.lib().tsg_test_windowable_rows(scanner._rs, rows.ctypes.data, n.value, ctypes.byref(n), ctypes.byref(nr)))
+    return rows[:n.value], nr.value
+
+
+def regex_examined(pattern, text, pos, submatch=False, cut=None):
+    """(match end or -1, furthest byte index examined) of the anchored run of
+    pattern at text[pos] on text[:cut] (tsg_test_regex_examined).  Tests only."""
+    t = np.frombuffer(bytes(text[:cut] if cut is not None else text) or b"\0", dtype=np.uint8).copy()
+    n = len(text[:cut] if cut is not None else text)
+    end, ex = ctypes.c_long(), ctypes.c_size_t()
+    _lib.check(_lib.lib().tsg_test_regex_examined(pattern.encode(), t.ctypes.data, n, pos, 1 if submatch else 0,
+                                                  ctypes.byref(end), ctypes.byref(ex)))
+    return end.value, ex.value
+
+
+def _window_segment(res, k):
+    """Segment k's window record (tsg_result_window_segment): classes and insufficient files."""
+    rec = _lib.TsgWindowSegment()
+    _lib.check(_lib.lib().tsg_result_window_segment(res, k, ctypes.byref(rec)))
+
+    def arr(p, ctype, dtype, count):
+        if not count:
+            return np.zeros(0, dtype)
+        return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctype)), shape=(count,)).copy()
+    return {"cls": arr(rec.cls, ctypes.c_uint8, np.uint8, rec.nfiles),
+            "insufficient": arr(rec.insufficient, ctypes.c_uint32, np.uint32, rec.ninsufficient).tolist()}
+
+
+def scan_device_model_windows(scanner, args_list, chunk, window):
+    """CPU model of the device-only scan with windows (tsg_scan_device_model_opts):
+    (findings, gather record of the windowed round with "cls" and
+    "insufficient", gather record of the fallback round, stats).  Tests only."""
+    data, offsets = pack(args_list)
+    paths, lens, _keep = _lib.pack_paths([a.FilePath for a in args_list])
+    binary = np.array([1 if a.Binary else 0 for a in args_list] or [0], dtype=np.uint8)
+    res = ctypes.c_void_p()
+    opts = _lib.scan_opts(window)
+    _lib.check(_lib.lib().tsg_scan_device_model_opts(scanner._rs, data.ctypes.data, offsets.ctypes.data, len(args_list),
+                                                     paths, lens, binary.ctypes.data, chunk, ctypes.byref(opts), None,
+                                                     None, ctypes.byref(res)))
+    try:
+        out = _lib.result_json(res)
+        for s in out:
+            s.pop("Error", None)
+        rec = _gather_segment(res, 0)
+        rec.update(_window_segment(res, 0))
+        stats = _lib.result_gather_stats(res)
+        stats.update(_lib.result_gather_window_stats(res))
+        ns = ctypes.c_size_t()
+        _lib.check(_lib.lib().tsg_result_raw_segments(res, ctypes.byref(ns)))
+        return out, rec, _gather_segment(res, 1) if ns.value > 1 else None, stats
+    finally:
+        _lib.lib().tsg_result_free(res)
+
+
 def _gather_segment(res, k):
     """Segment k's gather record of a result (tsg_result_gather_segment) as a dict."""
     rec = _lib.TsgGatherSegment()
@@ -1368,14 +1472,17 @@ def scan_device_model(scanner, args_list, chunk, with_gather=False):
         _lib.lib().tsg_result_free(res)
 
 
-def scan_device_raw(scanner, args_list, base=0, pad=16, tail=None, device="cuda:0"):
+def scan_device_raw(scanner, args_list, base=0, pad=16, tail=None, device="cuda:0", window=None):
     """tsg_scan_batch_device with the raw-output and keep-gather hooks on (they
     stay on for the scanner's engine).  The batch lies `base` bytes (a multiple
     of 16) above a 256-byte boundary of a device tensor that ends `pad` bytes
     after the batch; no host array of the batch is passed to the call.
     Returns (findings, {(file, rule): starts}, info) as scan_raw, each
     info["segments"][k] also holding "gather" (_gather_segment), and
-    info["gather_stats"].  Tests only."""
+    info["gather_stats"].  window: tsg_scan_batch_device_opts' windows; each
+    segment's "gather" then also holds "cls" and "insufficient",
+    info["gather_stats"] the window stats and info["fallback"] the fallback
+    round's gather record over the batch (None: no file fell back).  Tests only."""
     import torch
     L = _lib.lib()
     data, offsets = pack(args_list)
@@ -1395,22 +1502,35 @@ def scan_device_raw(scanner, args_list, base=0, pad=16, tail=None, device="cuda:
     torch.cuda.synchronize()
     res = ctypes.c_void_p()
     try:
-        _lib.check(L.tsg_scan_batch_device(eng, ctypes.c_void_p(full.data_ptr() + base), offsets.ctypes.data,
-                                           len(args_list), paths, lens, binary.ctypes.data, ctypes.byref(res)))
+        if window is not None:
+            opts = _lib.scan_opts(window)
+            _lib.check(L.tsg_scan_batch_device_opts(eng, ctypes.c_void_p(full.data_ptr() + base), offsets.ctypes.data,
+                                                    len(args_list), paths, lens, binary.ctypes.data, ctypes.byref(opts),
+                                                    ctypes.byref(res)))
+        else:
+            _lib.check(L.tsg_scan_batch_device(eng, ctypes.c_void_p(full.data_ptr() + base), offsets.ctypes.data,
+                                               len(args_list), paths, lens, binary.ctypes.data, ctypes.byref(res)))
         findings = _lib.result_json(res)
         for s in findings:
             s.pop("Error", None)
         ns = ctypes.c_size_t()
         _lib.check(L.tsg_result_raw_segments(res, ctypes.byref(ns)))
         segs = []
-        for k in range(ns.value):
+        wst = _lib.result_gather_window_stats(res) if window is not None else None
+        nseg = ns.value - (1 if wst and wst["fallback_files"] else 0)   # (the fallback round's record follows the segments')
+        for k in range(nseg):
             rec = _lib.TsgRawSegment()
             _lib.check(L.tsg_result_raw_segment(res, k, ctypes.byref(rec)))
             sd = {f: getattr(rec, f) for f in ("f0", "nfiles", "lead", "chunk_bytes", "b0", "bytes", "lead_bytes")}
             sd["gather"] = _gather_segment(res, k)
+            if window is not None:
+                sd["gather"].update(_window_segment(res, k))
             segs.append(sd)
         info = {"flags": _result_file_flags(res), "segments": segs, "stats": _lib.result_stats(res),
                 "gather_stats": _lib.result_gather_stats(res)}
+        if window is not None:
+            info["gather_stats"].update(wst)
+            info["fallback"] = _gather_segment(res, nseg) if nseg < ns.value else None
         return findings, _result_candidates(res), info
     finally:
         if res:
