@@ -208,6 +208,41 @@ typedef struct tsg_device_scan_opts {
 int tsg_scan_batch_device_opts(tsg_engine* e, const void* d_data, const uint64_t* offsets, uint32_t nfiles,
                                const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
                                const tsg_device_scan_opts* opts, tsg_result** out);
+/* ... with line windows: a window whose size comes from the data.  The
+ * confirmer reads lines -- the line of the match, the two above it and the
+ * lines below -- so a fixed span fails on every long line.  With
+ * window_line_cap != 0 the window of a candidate start s (s < len) of a
+ * windowed file of len bytes is [a, b), with t = min(len, s + window_after):
+ *   B  the position of the 3rd '\n' met walking back from s - 1 (the
+ *      confirmer's line search has to find that byte, so it belongs to the
+ *      window), never below max(0, s - window_line_cap); with fewer than 3
+ *      there, that lower end;
+ *   a  = min(s > window_before ? s - window_before : 0, B);
+ *   N  = 2 + the number of '\n' in [s, t);
+ *   E  the position just past the N-th '\n' at or after t, never past
+ *      min(len, t + window_line_cap); with fewer than N there, that upper end;
+ *   b  = max(t, E), and s + 1 at least.
+ * The GPU finds the K1 chunks of [a, b) from the bytes at both ends and the
+ * newline count it keeps per chunk; everything else -- the head chunk, the
+ * files that stay whole, the half-of-the-chunks rule, the fallback round -- is
+ * as above, on the widened windows.  A file with a line longer than the cap,
+ * or a match longer than window_after, still falls back.  The result is
+ * tsg_scan_batch_resident's, byte for byte, for every setting.
+ * struct_size: sizeof(tsg_device_scan_opts2) as the caller compiled it (a
+ * smaller value than the fields above need is an error).  window_line_cap 0:
+ * tsg_scan_batch_device_opts with the same windows, in every respect;
+ * window_line_cap != 0 with both window sizes 0 is an error.
+ * tsg_scan_batch_device_opts forwards here with cap 0. */
+typedef struct tsg_device_scan_opts2 {
+  uint32_t struct_size;
+  uint32_t window_before;
+  uint32_t window_after;
+  uint32_t window_line_cap;  /* bytes a line walk may go from s back and from t on; 0: byte windows alone */
+  uint64_t window_min_file;
+} tsg_device_scan_opts2;
+int tsg_scan_batch_device_opts2(tsg_engine* e, const void* d_data, const uint64_t* offsets, uint32_t nfiles,
+                                const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
+                                const tsg_device_scan_opts2* opts, tsg_result** out);
 
 /* Host-feed ceiling: stream `bytes` of host memory (pinned for full rate) to
  * HBM through the engine's upload path in segments, with no kernels; *ms =
@@ -258,6 +293,12 @@ int tsg_result_gather_stats(const tsg_result* r, uint64_t* files, uint64_t* byte
  * that crossed for the confirmer.  Any pointer may be NULL. */
 int tsg_result_gather_window_stats(const tsg_result* r, uint64_t* window_files, uint64_t* window_runs,
                                    uint64_t* window_bytes, uint64_t* fallback_files, uint64_t* fallback_bytes);
+/* ... with a line cap (all 0 otherwise): candidates whose line window covers
+ * more K1 chunks than their byte window (a repeated candidate counts again),
+ * candidates whose walk ended at the cap on either side, and the line pass's
+ * own kernel time, which tsg_result_gather_stats' ms includes.  Any pointer
+ * may be NULL. */
+int tsg_result_gather_line_stats(const tsg_result* r, uint64_t* widened, uint64_t* capped, double* ms);
 /* Frees a result; one of >= 4096 files + findings is handed to a background
    thread (its memory returns shortly after the call). */
 void tsg_result_free(tsg_result* r);

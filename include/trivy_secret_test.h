@@ -158,7 +158,16 @@ int tsg_scan_device_model_release(const tsg_ruleset* rs, const uint8_t* data, co
  * its segments' (index tsg_result_raw_segments - 1): the fallback round's
  * gather over the batch's files -- need, goff into the round's one buffer, the
  * run table with sources in the batch's frame, the bytes, the buffer's
- * capacity and whether the guard pattern behind it was whole. */
+ * capacity and whether the guard pattern behind it was whole.
+ *
+ * With a line cap (tsg_device_scan_opts2.window_line_cap):
+ * tsg_test_plan_gather_lines is tsg_test_plan_gather_windows with the frame's
+ * bytes (data: offsets[nfiles] bytes; csrc/gather.h line_window walks them
+ * directly, with no table) and the two line counters (may be NULL); it also
+ * runs the device pass's walk (line_window_chunks, on the '\n' count per
+ * chunk of `data`) and fails with TSG_ERR_INTERNAL when the two plans differ;
+ * tsg_scan_device_model_opts2 is tsg_scan_device_model_opts with the cap,
+ * fallback round included.  Cap 0 gives the plain functions' output. */
 typedef struct {
   uint32_t nfiles;
   const uint8_t* cls;
@@ -178,6 +187,16 @@ int tsg_scan_device_model_opts(const tsg_ruleset* rs, const uint8_t* data, const
                                const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
                                uint32_t chunk, const tsg_device_scan_opts* opts, void (*release)(void* user),
                                void* user, tsg_result** out);
+int tsg_test_plan_gather_lines(const uint8_t* data, const uint64_t* offsets, uint32_t nfiles, uint32_t lead,
+                               const uint32_t* cand_files, const uint32_t* cand_rules, const uint64_t* cand_starts,
+                               size_t ncands, const uint32_t* fflags, int all, const uint8_t* windowable,
+                               uint32_t nrows, uint32_t chunk, const tsg_device_scan_opts2* opts, uint8_t* cls,
+                               uint32_t* first_run, uint8_t* marks, uint64_t* runs, size_t runs_cap, size_t* nruns,
+                               uint64_t* total, uint64_t* widened, uint64_t* capped);
+int tsg_scan_device_model_opts2(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* offsets, uint32_t nfiles,
+                                const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
+                                uint32_t chunk, const tsg_device_scan_opts2* opts, void (*release)(void* user),
+                                void* user, tsg_result** out);
 
 /* CPU model of tsg_prepare_batch_device (csrc/prep.h: plan_prep, the device
  * pass stated sequentially with its per-byte rule: a byte of a binary .pyc is

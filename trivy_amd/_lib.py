@@ -56,6 +56,11 @@ class TsgDeviceScanOpts(ctypes.Structure):
                 ("window_min_file", ctypes.c_uint64)]
 
 
+class TsgDeviceScanOpts2(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("window_before", ctypes.c_uint32), ("window_after", ctypes.c_uint32),
+                ("window_line_cap", ctypes.c_uint32), ("window_min_file", ctypes.c_uint64)]
+
+
 class TsgWindowSegment(ctypes.Structure):
     _fields_ = [("nfiles", ctypes.c_uint32), ("cls", ctypes.c_void_p), ("insufficient", ctypes.c_void_p),
                 ("ninsufficient", ctypes.c_size_t)]
@@ -107,7 +112,23 @@ SIGNATURES = [
     ("tsg_scan_batch_device_opts", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                                    c_char_pp, ctypes.c_void_p, ctypes.c_void_p,
                                                    ctypes.POINTER(TsgDeviceScanOpts), ctypes.POINTER(ctypes.c_void_p)]),
+    ("tsg_scan_batch_device_opts2", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                    c_char_pp, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.POINTER(TsgDeviceScanOpts2), ctypes.POINTER(ctypes.c_void_p)]),
     ("tsg_result_gather_window_stats", ctypes.c_int, [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_uint64)] * 5),
+    ("tsg_result_gather_line_stats", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
+                                                     ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)]),
+    ("tsg_test_plan_gather_lines", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                   ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32,
+                                                   ctypes.c_uint32, ctypes.POINTER(TsgDeviceScanOpts2), ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                   ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint64),
+                                                   ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    ("tsg_scan_device_model_opts2", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                    c_char_pp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                    ctypes.POINTER(TsgDeviceScanOpts2), ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.POINTER(ctypes.c_void_p)]),
     ("tsg_test_plan_gather_windows", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                                      ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
@@ -460,6 +481,24 @@ def scan_opts(window):
         return None
     before, after, min_file = window
     return TsgDeviceScanOpts(int(before), int(after), int(min_file))
+
+
+def scan_opts2(window, window_lines):
+    """tsg_device_scan_opts2 from window = (before, after, min_file) and the line cap (0: byte windows)."""
+    if window is None:
+        raise ValueError("window_lines needs window=(before, after, min_file)")
+    before, after, min_file = window
+    cap = int(window_lines)
+    if cap < 0 or cap > 0xffffffff:
+        raise ValueError("window_lines must be a byte count below 4 GiB")
+    return TsgDeviceScanOpts2(ctypes.sizeof(TsgDeviceScanOpts2), int(before), int(after), cap, int(min_file))
+
+
+def result_gather_line_stats(res):
+    """What the line windows of a tsg_scan_batch_device_opts2 result did (tsg_result_gather_line_stats)."""
+    w, c, ms = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_double()
+    check(lib().tsg_result_gather_line_stats(res, ctypes.byref(w), ctypes.byref(c), ctypes.byref(ms)))
+    return {"line_widened": w.value, "line_capped": c.value, "line_ms": ms.value}
 
 
 def result_gather_window_stats(res):

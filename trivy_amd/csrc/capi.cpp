@@ -262,15 +262,58 @@ int tsg_scan_batch_device(tsg_engine* e, const void* d_data, const uint64_t* off
   TSG_API_CATCH
 }
 
-int tsg_scan_batch_device_opts(tsg_engine* e, const void* d_data, const uint64_t* offsets, uint32_t nfiles,
-                               const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
-                               const tsg_device_scan_opts* opts, tsg_result** out) {
+// opts2 -> the engine's options; false (with the error set) for a struct too small or a cap without windows
+static bool window_opts_of(const tsg_device_scan_opts2* opts, GatherWindowOpts* win, int* rc) {
+  if (!opts) return true;
+  if (opts->struct_size < sizeof(tsg_device_scan_opts2)) {
+    *rc = fail(TSG_ERR_INVALID, "tsg_device_scan_opts2.struct_size is smaller than the struct");
+    return false;
+  }
+  win->before = opts->window_before; win->after = opts->window_after; win->min_file = opts->window_min_file;
+  win->line_cap = opts->window_line_cap;
+  if (win->line_cap != 0 && !win->on()) {
+    *rc = fail(TSG_ERR_INVALID, "window_line_cap needs window_before or window_after");
+    return false;
+  }
+  return true;
+}
+
+static tsg_device_scan_opts2 opts2_of(const tsg_device_scan_opts& o) {
+  tsg_device_scan_opts2 o2;
+  o2.struct_size = sizeof(o2);
+  o2.window_before = o.window_before; o2.window_after = o.window_after; o2.window_line_cap = 0;
+  o2.window_min_file = o.window_min_file;
+  return o2;
+}
+
+int tsg_scan_batch_device_opts2(tsg_engine* e, const void* d_data, const uint64_t* offsets, uint32_t nfiles,
+                                const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
+                                const tsg_device_scan_opts2* opts, tsg_result** out) {
   TSG_API_TRY
   if (!d_data) return fail(TSG_ERR_INVALID, "d_data is NULL");
   GatherWindowOpts win;
-  if (opts) { win.before = opts->window_before; win.after = opts->window_after; win.min_file = opts->window_min_file; }
+  int rc = TSG_OK;
+  if (!window_opts_of(opts, &win, &rc)) return rc;
   return do_scan(e, d_data, nullptr, offsets, nfiles, paths, path_lens, binary, out, /*device_only=*/true,
                  win.on() ? &win : nullptr);
+  TSG_API_CATCH
+}
+
+int tsg_scan_batch_device_opts(tsg_engine* e, const void* d_data, const uint64_t* offsets, uint32_t nfiles,
+                               const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
+                               const tsg_device_scan_opts* opts, tsg_result** out) {
+  if (!opts) return tsg_scan_batch_device_opts2(e, d_data, offsets, nfiles, paths, path_lens, binary, nullptr, out);
+  const tsg_device_scan_opts2 o2 = opts2_of(*opts);
+  return tsg_scan_batch_device_opts2(e, d_data, offsets, nfiles, paths, path_lens, binary, &o2, out);
+}
+
+int tsg_result_gather_line_stats(const tsg_result* r, uint64_t* widened, uint64_t* capped, double* ms) {
+  TSG_API_TRY
+  if (!r) return fail(TSG_ERR_INVALID, "result is NULL");
+  if (widened) *widened = r->stats.line_widened;
+  if (capped) *capped = r->stats.line_capped;
+  if (ms) *ms = r->stats.line_ms;
+  return TSG_OK;
   TSG_API_CATCH
 }
 
@@ -1037,18 +1080,49 @@ int tsg_test_plan_gather_windows(const uint64_t* offsets, uint32_t nfiles, uint3
                                  const uint32_t* fflags, int all, const uint8_t* windowable, uint32_t nrows,
                                  uint32_t chunk, const tsg_device_scan_opts* opts, uint8_t* cls, uint32_t* first_run,
                                  uint8_t* marks, uint64_t* runs, size_t runs_cap, size_t* nruns, uint64_t* total) {
+  if (!opts) return fail(TSG_ERR_INVALID, "bad argument");
+  const tsg_device_scan_opts2 o2 = opts2_of(*opts);
+  return tsg_test_plan_gather_lines(nullptr, offsets, nfiles, lead, cand_files, cand_rules, cand_starts, ncands, fflags,
+                                    all, windowable, nrows, chunk, &o2, cls, first_run, marks, runs, runs_cap, nruns,
+                                    total, nullptr, nullptr);
+}
+
+int tsg_test_plan_gather_lines(const uint8_t* data, const uint64_t* offsets, uint32_t nfiles, uint32_t lead,
+                               const uint32_t* cand_files, const uint32_t* cand_rules, const uint64_t* cand_starts,
+                               size_t ncands, const uint32_t* fflags, int all, const uint8_t* windowable,
+                               uint32_t nrows, uint32_t chunk, const tsg_device_scan_opts2* opts, uint8_t* cls,
+                               uint32_t* first_run, uint8_t* marks, uint64_t* runs, size_t runs_cap, size_t* nruns,
+                               uint64_t* total, uint64_t* widened, uint64_t* capped) {
   TSG_API_TRY
   if (!offsets || !fflags || !opts || !cls || !first_run || !nruns || !total || chunk == 0 || lead > nfiles ||
       (ncands && (!cand_files || !cand_rules || !cand_starts)) || (nrows && !windowable))
     return fail(TSG_ERR_INVALID, "bad argument");
+  if (opts->struct_size < sizeof(tsg_device_scan_opts2)) return fail(TSG_ERR_INVALID, "struct_size is smaller than the struct");
+  if (opts->window_line_cap != 0 && !data && nfiles && offsets[nfiles]) return fail(TSG_ERR_INVALID, "a line cap needs the data");
   for (uint32_t i = 0; i < nfiles; ++i)
     if (offsets[i + 1] < offsets[i]) return fail(TSG_ERR_INVALID, "offsets must be non-decreasing");
   std::vector<GatherCand> cands(ncands);
   for (size_t k = 0; k < ncands; ++k) cands[k] = GatherCand{cand_files[k], cand_rules[k], cand_starts[k]};
   GatherWindowOpts o;
   o.before = opts->window_before; o.after = opts->window_after; o.min_file = opts->window_min_file;
+  o.line_cap = opts->window_line_cap;
   GatherWindowPlan wp;
-  plan_gather_windows(offsets, nfiles, lead, cands.data(), ncands, fflags, all != 0, windowable, nrows, chunk, o, &wp);
+  plan_gather_windows(offsets, nfiles, lead, cands.data(), ncands, fflags, all != 0, windowable, nrows, chunk, o, &wp, data);
+  if (widened) *widened = wp.widened;
+  if (capped) *capped = wp.capped;
+  if (o.line_cap != 0 && data) {
+    // the walk the device pass runs (line_window_chunks over the '\n' count per chunk, as K1 leaves it) must
+    // give the plan the byte model gave
+    const uint64_t nbytes = nfiles ? offsets[nfiles] : 0;
+    std::vector<uint16_t> nl((nbytes + chunk - 1) / chunk + 1, 0);
+    if (chunk > 32768) return fail(TSG_ERR_INVALID, "chunk exceeds K1's");
+    for (uint64_t x = 0; x < nbytes; ++x) nl[x / chunk] += data[x] == '\n';
+    GatherWindowPlan tp;
+    plan_gather_windows(offsets, nfiles, lead, cands.data(), ncands, fflags, all != 0, windowable, nrows, chunk, o, &tp,
+                        data, nl.data());
+    if (tp.cls != wp.cls || tp.marks != wp.marks || tp.widened != wp.widened || tp.capped != wp.capped)
+      return fail(TSG_ERR_INTERNAL, "line windows: the table walk and the byte model differ");
+  }
   std::copy(wp.cls.begin(), wp.cls.end(), cls);
   std::copy(wp.first_run.begin(), wp.first_run.end(), first_run);
   if (marks) std::copy(wp.marks.begin(), wp.marks.end(), marks);
@@ -1112,9 +1186,19 @@ int tsg_scan_device_model_opts(const tsg_ruleset* rs, const uint8_t* data, const
                                const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
                                uint32_t chunk, const tsg_device_scan_opts* opts, void (*release)(void* user),
                                void* user, tsg_result** out) {
+  if (!opts) return tsg_scan_device_model_opts2(rs, data, offsets, nfiles, paths, path_lens, binary, chunk, nullptr, release, user, out);
+  const tsg_device_scan_opts2 o2 = opts2_of(*opts);
+  return tsg_scan_device_model_opts2(rs, data, offsets, nfiles, paths, path_lens, binary, chunk, &o2, release, user, out);
+}
+
+int tsg_scan_device_model_opts2(const tsg_ruleset* rs, const uint8_t* data, const uint64_t* offsets, uint32_t nfiles,
+                                const char* const* paths, const uint32_t* path_lens, const uint8_t* binary,
+                                uint32_t chunk, const tsg_device_scan_opts2* opts, void (*release)(void* user),
+                                void* user, tsg_result** out) {
   TSG_API_TRY
   GatherWindowOpts win;
-  if (opts) { win.before = opts->window_before; win.after = opts->window_after; win.min_file = opts->window_min_file; }
+  int rc = TSG_OK;
+  if (!window_opts_of(opts, &win, &rc)) return rc;
   if (!rs || !out || !offsets || (nfiles && (!paths || !data)) || chunk == 0) return fail(TSG_ERR_INVALID, "NULL argument");
   std::string err;
   // an engine without devices for this call, around the models' compiled prefilter

@@ -138,7 +138,7 @@ bool Engine::model_scan_windows(const BatchInput& in, uint32_t chunk, SegmentOut
   const std::vector<uint8_t> wrows = windowable_rows();
   GatherWindowPlan wp;
   plan_gather_windows(in.offsets, nfiles, 0, reinterpret_cast<const GatherCand*>(g.cands.data()), g.cands.size(),
-                      g.ff.data(), all, wrows.data(), static_cast<uint32_t>(wrows.size()), chunk, win, &wp);
+                      g.ff.data(), all, wrows.data(), static_cast<uint32_t>(wrows.size()), chunk, win, &wp, in.h_data);
   // every run in an allocation of exactly its bytes
   std::vector<std::vector<uint8_t>> run_bytes(wp.runs.size());
   for (size_t k = 0; k < wp.runs.size(); ++k) {
@@ -215,6 +215,8 @@ bool Engine::model_scan_windows(const BatchInput& in, uint32_t chunk, SegmentOut
     st->window_bytes = wp.total;
     st->fallback_files = insufficient.size();
     st->fallback_bytes = fp.total;
+    st->line_widened = wp.widened;
+    st->line_capped = wp.capped;
   }
   if (raw) {
     *raw = RawScan();

@@ -56,6 +56,11 @@ struct ScanStats {
   // and bytes of the fallback round (files fetched whole after all).
   // gather_bytes and gather_runs hold both rounds.
   uint64_t window_files = 0, window_runs = 0, window_bytes = 0, fallback_files = 0, fallback_bytes = 0;
+  // ... with a line cap (gather.h line_window): candidates whose window covers
+  // more chunks than the byte window, candidates whose walk ended at the cap,
+  // and the line pass's own time (part of gather_ms)
+  uint64_t line_widened = 0, line_capped = 0;
+  double line_ms = 0;
 };
 
 // A batch scan stage: results[i] = Scan(ScanArgs{paths[i], data[off[i]:off[i+1]],

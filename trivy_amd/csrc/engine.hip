@@ -1642,10 +1642,10 @@ struct LaneStreams {
   hipEvent_t wire_raw_ev[4] = {};
   hipEvent_t wire_copies_done[2] = {};
   hipEvent_t wire_copy2_done[2] = {};
-  hipEvent_t gev[2] = {};                       // device-only scans: the gather kernels' start / end (compute stream)
+  hipEvent_t gev[4] = {};                       // device-only scans: the gather kernels' start / end (compute stream); [2], [3]: tsg_gw_lines' own
   ~LaneStreams() {
     for (hipEvent_t* e : {&ev[0], &ev[1], &ev[2], &ev[3], &ev_sync, &up_begin[0], &up_begin[1], &up_done[0], &up_done[1],
-                          &gev[0], &gev[1],
+                          &gev[0], &gev[1], &gev[2], &gev[3],
                           &anchor, &wire_raw_ev[0], &wire_raw_ev[1], &wire_raw_ev[2], &wire_raw_ev[3],
                           &wire_copies_done[0], &wire_copies_done[1], &wire_copy2_done[0], &wire_copy2_done[1]})
       if (*e) (void)hipEventDestroy(*e);
@@ -2036,6 +2036,7 @@ void add_stats(ScanStats* a, const ScanStats& s) {
   a->gather_bytes += s.gather_bytes; a->gather_runs += s.gather_runs; a->gather_ms += s.gather_ms;
   a->gather_retries += s.gather_retries;
   a->window_runs += s.window_runs; a->window_bytes += s.window_bytes;
+  a->line_widened += s.line_widened; a->line_capped += s.line_capped; a->line_ms += s.line_ms;
 }
 
 }  // namespace
@@ -2356,7 +2357,7 @@ bool Engine::seg_size_scratch(SegRun& r, std::string* err) {
          (!r.gather || r.win || (ln.d_need.ensure(in.nfiles, err) && ln.d_goff.ensure(in.nfiles, err) &&
                         ln.d_gruns.ensure((static_cast<size_t>(in.nfiles) + 1) / 2 + 1, err) && ln.d_gmeta.ensure(2, err))) &&
          (!r.win || (ln.d_gw.ensure(gather_windows_scratch_bytes(r.nchunks, in.nfiles), err) &&
-                     ln.d_gcls.ensure(in.nfiles, err) && ln.d_gmeta.ensure(2, err)));
+                     ln.d_gcls.ensure(in.nfiles, err) && ln.d_gmeta.ensure(4, err)));
 }
 
 // K1's grid for this attempt, and the prologue: keyword bits, file flags,
@@ -2562,9 +2563,9 @@ bool Engine::seg_readback_wait(SegRun& r, int a2, std::string* err) {
     // the gather's layout rides the same round trip (a launch of its own:
     // tsg_readback's region list is full); need and the run table only for
     // tsg_test_keep_gather
-    if (!ln.rb_gmeta.ensure_readback(16, err)) return false;
+    if (!ln.rb_gmeta.ensure_readback(32, err)) return false;
     Readbacks rg;
-    rg.add(ln.d_gmeta.p, ln.rb_gmeta, 4);
+    rg.add(ln.d_gmeta.p, ln.rb_gmeta, r.win ? 8 : 4);      // (with windows: tsg_gw_lines' two counters behind the totals)
     if (r.win) {
       // with windows: the files' classes and the run table (the host places the files from it)
       if (!ln.rb_gcls.ensure_readback(nfiles, err) || !ln.rb_gruns.ensure_readback(r.runs_cap * sizeof(GatherRun), err))
@@ -2652,7 +2653,7 @@ bool Engine::seg_launch_gather(SegRun& r, GpuOut* out, std::string* err) {
   if (!(r.win ? gather_windows_launch(ln.d_cands.p, ln.d_cnt.p + 1, static_cast<uint32_t>(ln.cand_cap), ln.d_ff.p, r.d_off,
                                       r.in.nfiles, r.lead, all, r.dt.wrows.p, r.dt.nrows, r.chunk, r.total, *r.win,
                                       gather_windows_scratch_layout(ln.d_gw.p, r.nchunks, r.in.nfiles), ln.d_gcls.p,
-                                      ln.d_gruns.p, r.runs_cap, ln.d_gmeta.p, s, err)
+                                      ln.d_gruns.p, r.runs_cap, ln.d_gmeta.p, s, err, r.d_data, ln.d_nl.p, ln.gev[2], ln.gev[3])
               : gather_plan_launch(ln.d_cands.p, ln.d_cnt.p + 1, static_cast<uint32_t>(ln.cand_cap), ln.d_ff.p, r.d_off,
                           r.in.nfiles, r.lead, all, r.chunk, ln.d_need.p, ln.d_goff.p, ln.d_gruns.p, ln.d_gmeta.p, s, err)) ||
       !gather_copy_launch(r.d_data, ln.d_gruns.p, ln.d_gmeta.p, static_cast<uint8_t*>(out->gather.b->mem.d),
@@ -2710,6 +2711,13 @@ bool Engine::seg_gather_retry(SegRun& r, GpuOut* out, std::string* err) {
     out->n_gruns = static_cast<size_t>(nruns);
     r.st->window_bytes += total;
     r.st->window_runs += nruns;
+    if (r.win->line_cap != 0) {
+      float lms = 0;
+      HIP_OK(hipEventElapsedTime(&lms, ln.gev[2], ln.gev[3]));
+      r.st->line_ms += lms;
+      r.st->line_widened += meta[2];
+      r.st->line_capped += meta[3];
+    }
   } else {
     out->rb_goff = ln.rb_goff.as<uint64_t>();
     out->n_goff = r.in.nfiles;

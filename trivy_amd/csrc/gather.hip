@@ -23,6 +23,9 @@
 //   tsg_gw_class     per file: none / whole / windowed before the windows are
 //                    counted; a windowed file's head chunk is marked
 //   tsg_gw_windows   per candidate of a windowed file: its window's chunks
+//   tsg_gw_lines     in its place with a line cap: a wave per candidate widens
+//                    the window to the lines the confirmer reads, from the
+//                    bytes at the window's ends and K1's per-chunk '\n' counts
 //   tsg_gw_count     per marked chunk: one more for every windowed file on it
 //   tsg_gw_demote    per file: windows on more than half of its chunks -> whole
 //   tsg_gw_fill      per chunk: marked when a whole file lies on it
@@ -220,6 +223,111 @@ __global__ __launch_bounds__(256) void tsg_gw_windows(const uint4* __restrict__ 
   }
 }
 
+// '\n' among the frame's bytes [p0, p1), counted by the whole wave: lane l
+// takes the aligned 16-byte words l, l + 64, ... of the span, a SWAR compare
+// per dword, the bytes outside [p0, p1) masked off; a butterfly of __shfl_xor
+// leaves the sum in every lane.  The callers keep the span inside one K1
+// chunk (at most 32 KiB: 32 words a lane).  The first word starts at p0
+// rounded down -- the frame is 16-byte aligned, so at or above byte 0 -- and
+// the last ends below p1 + 16: p1 is at most the segment's bytes, behind
+// which the frame guarantees 16 readable bytes (the guarantee
+// gather_copy_launch's whole-word copy relies on, gather_dev.h).
+__device__ __forceinline__ uint32_t wave_count_nl(const uint8_t* __restrict__ data, uint64_t p0, uint64_t p1,
+                                                  uint32_t lane) {
+  uint32_t c = 0;
+  if (p1 > p0) {
+    const uint64_t w1 = (p1 + 15) >> 4;
+    for (uint64_t w = (p0 >> 4) + lane; w < w1; w += 64) {
+      const uint64_t wb = w << 4;
+      const v4u x = *reinterpret_cast<const v4u*>(data + wb);
+      const uint32_t cut_lo = p0 > wb ? static_cast<uint32_t>(p0 - wb) : 0u;             // 0 .. 15
+      const uint32_t cut_hi = p1 - wb < 16 ? static_cast<uint32_t>(p1 - wb) : 16u;       // 1 .. 16
+      const uint32_t valid = ((1u << cut_hi) - 1u) & ~((1u << cut_lo) - 1u);             // one bit per byte
+      const uint32_t d[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const uint32_t y = d[k] ^ 0x0a0a0a0au;                                           // a zero byte where '\n' stood
+        const uint32_t z = ~(((y & 0x7f7f7f7fu) + 0x7f7f7f7fu) | y | 0x7f7f7f7fu);       // 0x80 per zero byte, exact
+        const uint32_t v = (valid >> (4 * k)) & 15u;
+        const uint32_t keep = ((v & 1u) << 7) | ((v & 2u) << 14) | ((v & 4u) << 21) | ((v & 8u) << 28);
+        c += __popc(z & keep);
+      }
+    }
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
+  return __builtin_amdgcn_readfirstlane(c);
+}
+
+// Line windows (gather.h: line_window is the byte model, line_window_chunks
+// the walk run here): in place of tsg_gw_windows when line_cap != 0.  One wave
+// per candidate of a windowed file: a wave reads 64 records, a lane each, and
+// then takes the eligible ones in turn, every lane running the same walk --
+// bytes are counted by the whole wave (wave_count_nl) only in the partial
+// chunks at s and t and over [s, t); in between, K1's per-chunk counts (nl) of
+// chunks that lie wholly inside the file are summed.  Every nl index lies
+// strictly between two chunks of the file, [c0, c1] with c1 < nchunks checked
+// first; every byte read lies in [file start, file end) but for the aligned
+// words at its ends (wave_count_nl).
+// stats: [0] candidates whose chunks exceed the byte window's, [1] candidates
+// whose walk ended at the cap.
+__global__ __launch_bounds__(256) void tsg_gw_lines(const uint4* __restrict__ cands,
+                                                    const uint32_t* __restrict__ ncands, uint32_t cand_cap,
+                                                    const uint64_t* __restrict__ off, uint32_t nfiles, uint32_t lead,
+                                                    const uint8_t* __restrict__ cls, uint8_t* __restrict__ whole,
+                                                    uint8_t* __restrict__ marks, uint32_t chunk, uint64_t nchunks,
+                                                    uint32_t before, uint32_t after, uint32_t line_cap,
+                                                    const uint8_t* __restrict__ data,
+                                                    const uint16_t* __restrict__ nl,
+                                                    unsigned long long* __restrict__ stats) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t wave = static_cast<uint64_t>(blockIdx.x) * kGwWaves + (threadIdx.x >> 6);
+  const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * kGwWaves;
+  const uint32_t n = min(*ncands, cand_cap);
+  uint32_t widened = 0, capped = 0;
+  for (uint64_t base = wave * 64; base < n; base += nwaves * 64) {
+    const uint64_t i = base + lane;
+    uint32_t f = 0, s_lo = 0, s_hi = 0;
+    bool ok = false;
+    if (i < n) {
+      const uint4 c = cands[i];
+      f = c.x; s_lo = c.z; s_hi = c.w;
+      if (f >= lead && f < nfiles && cls[f] == kGatherClassWindow) {
+        const uint64_t start = s_lo | (static_cast<uint64_t>(s_hi) << 32);
+        ok = start < off[f + 1] - off[f];          // (tsg_gw_flags made a file with a start past it whole)
+      }
+    }
+    uint64_t todo = __ballot(ok);
+    while (todo) {
+      const int src = __ffsll(static_cast<long long>(todo)) - 1;
+      todo &= todo - 1;
+      const uint32_t cf = __builtin_amdgcn_readlane(f, src);
+      const uint64_t s = static_cast<uint32_t>(__builtin_amdgcn_readlane(s_lo, src)) |
+                         (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readlane(s_hi, src))) << 32);
+      const uint64_t o = off[cf], len = off[cf + 1] - o;
+      const uint64_t c0 = o / chunk, c1 = (o + len - 1) / chunk;
+      if (c1 >= nchunks || c1 < c0) { if (lane == 0) whole[cf] = 1; continue; }
+      // the byte window, as tsg_gw_windows, and the line window's chunks (gather.h: the model runs the same walk)
+      uint64_t plo, phi, lo, hi;
+      bool cap_hit;
+      window_chunks(o, len, s, before, after, chunk, &plo, &phi);
+      line_window_chunks(o, len, s, before, after, line_cap, chunk, nl,
+                         [data, lane](uint64_t p0, uint64_t p1) { return wave_count_nl(data, p0, p1, lane); }, &lo, &hi,
+                         &cap_hit);
+      // (every chunk above is one of the file's: c0 <= lo <= hi <= c1 < nchunks; checked all the same)
+      if (lo < c0 || hi > c1 || hi >= nchunks || lo > hi) { if (lane == 0) whole[cf] = 1; continue; }
+      widened += lo < plo || hi > phi;
+      capped += cap_hit;
+      if (2 * (hi - lo + 1) > c1 - c0 + 1) { if (lane == 0) whole[cf] = 1; continue; }
+      for (uint64_t k = lo + lane; k <= hi; k += 64) marks[k] = 1;
+    }
+  }
+  if (lane == 0) {
+    if (widened) atomicAdd(stats, static_cast<unsigned long long>(widened));
+    if (capped) atomicAdd(stats + 1, static_cast<unsigned long long>(capped));
+  }
+}
+
 // the first file at or above lead that ends above byte b (nfiles: none)
 __device__ __forceinline__ uint32_t first_file_ending_above(const uint64_t* __restrict__ off, uint32_t nfiles,
                                                             uint32_t lead, uint64_t b) {
@@ -405,12 +513,15 @@ bool gather_windows_launch(const void* cands, const uint32_t* ncands, uint32_t c
                            const uint64_t* offsets, uint32_t nfiles, uint32_t lead, bool all, const uint8_t* wrows,
                            uint32_t nrows, uint32_t chunk, uint64_t total, const GatherWindowOpts& o,
                            const GatherWindowScratch& sc, uint8_t* cls, GatherRun* runs, uint64_t runs_cap,
-                           uint64_t* meta, hipStream_t s, std::string* err) {
+                           uint64_t* meta, hipStream_t s, std::string* err, const uint8_t* data, const uint16_t* nl,
+                           hipEvent_t lines_begin, hipEvent_t lines_end) {
   const uint64_t nchunks = (total + chunk - 1) / chunk, nreg64 = gw_regions(nchunks);
+  if (o.line_cap != 0 && (!data || !nl)) { *err = "gather windows: line windows need the frame and K1's newline counts"; return false; }
   if (chunk == 0 || chunk % 128 != 0 || nreg64 > 0xffffffffull / kGwWaves) { *err = "gather windows: chunk grid out of range"; return false; }
   const uint32_t nreg = static_cast<uint32_t>(nreg64);
   hipError_t e = hipMemsetAsync(sc.tot_m, 0, gather_windows_scratch_bytes(nchunks, nfiles), s);
   if (e == hipSuccess && nfiles) e = hipMemsetAsync(cls, 0, nfiles, s);
+  if (e == hipSuccess) e = hipMemsetAsync(meta + 2, 0, 16, s);          // tsg_gw_lines' counters
   if (e != hipSuccess) { *err = std::string("gather windows: ") + hipGetErrorString(e); return false; }
   // (grid-stride kernels: at most 1024 workgroups, as tsg_gather_mark's; the candidate passes cannot know the
   // list's length on the host and take the capacity's grid)
@@ -421,8 +532,16 @@ bool gather_windows_launch(const void* cands, const uint32_t* ncands, uint32_t c
   hipLaunchKernelGGL(tsg_gw_class, grid(nfiles), dim3(256), 0, s, offsets, nfiles, lead, fflags, all ? 1u : 0u,
                      o.min_file, static_cast<const uint8_t*>(sc.any), static_cast<const uint8_t*>(sc.whole), cls,
                      sc.marks, chunk, nchunks);
-  hipLaunchKernelGGL(tsg_gw_windows, grid(cand_cap), dim3(256), 0, s, cd, ncands, cand_cap, offsets, nfiles, lead,
-                     static_cast<const uint8_t*>(cls), sc.whole, sc.marks, chunk, nchunks, o.before, o.after);
+  if (o.line_cap != 0) {
+    if (lines_begin && (e = hipEventRecord(lines_begin, s)) != hipSuccess) { *err = std::string("gather windows: ") + hipGetErrorString(e); return false; }
+    hipLaunchKernelGGL(tsg_gw_lines, grid(cand_cap), dim3(256), 0, s, cd, ncands, cand_cap, offsets, nfiles, lead,
+                       static_cast<const uint8_t*>(cls), sc.whole, sc.marks, chunk, nchunks, o.before, o.after, o.line_cap,
+                       data, nl, reinterpret_cast<unsigned long long*>(meta + 2));
+    if (lines_end && (e = hipEventRecord(lines_end, s)) != hipSuccess) { *err = std::string("gather windows: ") + hipGetErrorString(e); return false; }
+  } else {
+    hipLaunchKernelGGL(tsg_gw_windows, grid(cand_cap), dim3(256), 0, s, cd, ncands, cand_cap, offsets, nfiles, lead,
+                       static_cast<const uint8_t*>(cls), sc.whole, sc.marks, chunk, nchunks, o.before, o.after);
+  }
   hipLaunchKernelGGL(tsg_gw_count, grid(nchunks), dim3(256), 0, s, static_cast<const uint8_t*>(sc.marks), nchunks,
                      offsets, nfiles, lead, static_cast<const uint8_t*>(cls), sc.cnt, chunk);
   hipLaunchKernelGGL(tsg_gw_demote, grid(nfiles), dim3(256), 0, s, offsets, nfiles, lead, cls,

@@ -42,11 +42,19 @@ GatherWindowScratch gather_windows_scratch_layout(void* scratch, uint64_t nchunk
 // windowable byte per rule-table row (wrows, nrows) and the window options.
 // total: the segment's bytes.  A table of more than runs_cap runs stores
 // nothing past it and sets meta[1] to UINT64_MAX (the copy then writes nothing).
+// Here meta has four words: with o.line_cap != 0 (gather.h line_window)
+// tsg_gw_lines leaves in [2] the candidates it widened and in [3] those that
+// ended at the cap; both are zero otherwise.  That pass reads the segment's
+// frame (data: 16-byte aligned, 16 readable bytes past its end, chunk 0 at
+// byte 0) and K1's '\n' count per chunk (nl), and is timed between
+// lines_begin and lines_end where given.  It needs no scratch of its own.
 bool gather_windows_launch(const void* cands, const uint32_t* ncands, uint32_t cand_cap, const uint32_t* fflags,
                            const uint64_t* offsets, uint32_t nfiles, uint32_t lead, bool all, const uint8_t* wrows,
                            uint32_t nrows, uint32_t chunk, uint64_t total, const GatherWindowOpts& o,
                            const GatherWindowScratch& sc, uint8_t* cls, GatherRun* runs, uint64_t runs_cap,
-                           uint64_t* meta, hipStream_t s, std::string* err);
+                           uint64_t* meta, hipStream_t s, std::string* err, const uint8_t* data = nullptr,
+                           const uint16_t* nl = nullptr, hipEvent_t lines_begin = nullptr,
+                           hipEvent_t lines_end = nullptr);
 
 // Enqueue on `s`: the runs' bytes from the segment's frame (src, 16-byte
 // aligned, 16 readable bytes past its end) into dst (host-mapped, cap bytes).

@@ -375,7 +375,7 @@ class Scanner:
         return out + ({"ms": ms, "rounds": rounds},) if with_stats else out
 
     def ScanLayersGzipDevice(self, blobs, skip_files=(), skip_dirs=(), file_patterns=(), config_path="",
-                             with_stats=False, contents=False, window=None):
+                             with_stats=False, contents=False, window=None, window_lines=None):
         """The layers of an image as the registry or `docker save` hands them
         over -- one gzip stream each -- scanned with only the compressed bytes
         and the confirmer's gather crossing the link:
@@ -393,11 +393,14 @@ class Scanner:
         ("unexpected EOF", "gzip: invalid checksum", ...); a malformed tar
         raises WalkError as PrepareLayerTarDevice does.  with_stats appends
         {"gz_bytes", "tar_bytes", "inflate_ms", "inflate_rounds"} to the list's
-        tuple: (layers, stats).  window: ScanBatchDevice's, for every layer's scan."""
+        tuple: (layers, stats).  window, window_lines: ScanBatchDevice's, for
+        every layer's scan."""
+        if window_lines is not None and window is None:
+            raise ValueError("window_lines needs window=(before, after, min_file)")
         views = self._blob_views(blobs)
         opts = dict(skip_files=skip_files, skip_dirs=skip_dirs, file_patterns=file_patterns, config_path=config_path)
         slots, st = self._gzip_layer_slots(views, list(range(len(views))))
-        layers = [self._scan_layer_slot(d_tar, k, opts, contents, window) for d_tar, k in slots]
+        layers = [self._scan_layer_slot(d_tar, k, opts, contents, window, window_lines) for d_tar, k in slots]
         if with_stats:
             return layers, {"gz_bytes": st["gz_bytes"], "tar_bytes": sum(k for _, k in slots), "inflate_ms": st["ms"],
                             "inflate_rounds": st["rounds"]}
@@ -444,10 +447,11 @@ class Scanner:
         slots = [(dst[int(do[k]):int(do[k + 1])], int(out_lens[k])) for k in range(len(idx))]
         return slots, {"gz_bytes": int(go[-1]), "ms": ist["ms"], "rounds": ist["rounds"]}
 
-    def _scan_layer_slot(self, d_tar, k, opts, contents, window=None):
+    def _scan_layer_slot(self, d_tar, k, opts, contents, window=None, window_lines=None):
         """PrepareLayerTarDevice -> ScanBatchDevice on a tar of k bytes in HBM: (ScanArgs list, walk dict, [types.Secret])"""
         p_dst, offs, scan_paths, binf, walk, _ms = self.PrepareLayerTarDevice(d_tar, k, **opts)
-        secrets = self.ScanBatchDevice(p_dst, offs, scan_paths, binf, window=window)
+        kw = {} if window_lines is None else {"window_lines": window_lines}
+        secrets = self.ScanBatchDevice(p_dst, offs, scan_paths, binf, window=window, **kw)
         data = p_dst[:int(offs[-1])].cpu().numpy().tobytes() if contents and len(scan_paths) else None
         args = [ScanArgs(p, data[int(offs[j]):int(offs[j + 1])] if data is not None else (b"" if contents else None),
                          bool(binf[j])) for j, p in enumerate(scan_paths)]
@@ -543,7 +547,7 @@ class Scanner:
         return int(_lib.lib().tsg_layer_compression(v.ctypes.data if len(v) else None, len(v)))
 
     def ScanLayersCompressedDevice(self, blobs, skip_files=(), skip_dirs=(), file_patterns=(), config_path="",
-                                   with_stats=False, contents=False, window=None):
+                                   with_stats=False, contents=False, window=None, window_lines=None):
         """ScanLayersGzipDevice for layers as layer.Uncompressed() takes them:
         each blob is a gzip stream, a zstd stream or a plain tar, told apart by
         its first bytes (tsg_layer_compression) as go-containerregistry's peek
@@ -557,8 +561,10 @@ class Scanner:
         Arguments and the per-layer result are ScanLayersGzipDevice's.  A
         stream that fails raises WalkError with its blob index and the status
         text.  with_stats appends {"gz_bytes", "zstd_bytes", "plain_bytes",
-        "tar_bytes", "inflate_ms", "zstd_ms", "inflate_rounds"}.  window:
-        ScanBatchDevice's, for every layer's scan."""
+        "tar_bytes", "inflate_ms", "zstd_ms", "inflate_rounds"}.  window,
+        window_lines: ScanBatchDevice's, for every layer's scan."""
+        if window_lines is not None and window is None:
+            raise ValueError("window_lines needs window=(before, after, min_file)")
         L = _lib.lib()
         views = self._blob_views(blobs)
         kinds = [int(L.tsg_layer_compression(v.ctypes.data, min(len(v), 4))) if len(v) else _lib.LAYER_NONE for v in views]
@@ -591,7 +597,7 @@ class Scanner:
             for k, i in enumerate(plain):
                 slots[i] = (d_p[int(po[k]):int(po[k + 1]) + (16 if k == len(plain) - 1 else 0)], len(views[i]))
                 stats["plain_bytes"] += len(views[i])
-        layers = [self._scan_layer_slot(d_tar, k, opts, contents, window) for d_tar, k in slots]
+        layers = [self._scan_layer_slot(d_tar, k, opts, contents, window, window_lines) for d_tar, k in slots]
         stats["tar_bytes"] = sum(k for _, k in slots)
         return (layers, stats) if with_stats else layers
 
@@ -633,7 +639,7 @@ class Scanner:
             s.pop("Error", None)
         return (out, stats) if with_stats else out
 
-    def _scan_device_tensor(self, d_data, offsets, paths, binary, h_data, with_stats, window=None):
+    def _scan_device_tensor(self, d_data, offsets, paths, binary, h_data, with_stats, window=None, window_lines=None):
         """tsg_scan_batch_device (h_data None) or tsg_scan_batch_resident on a
         uint8 device tensor; returns (findings, stats or None, C result)."""
         import torch
@@ -651,7 +657,14 @@ class Scanner:
         b = np.ascontiguousarray(binary if binary is not None else np.zeros(max(nfiles, 1)), dtype=np.uint8)
         torch.cuda.current_stream(d_data.device).synchronize()     # the engine runs on its own streams
         res = ctypes.c_void_p()
-        if h_data is None and window is not None:
+        if window_lines is not None and (h_data is not None or window is None):
+            raise ValueError("window_lines needs window=(before, after, min_file)")
+        if window_lines is not None:
+            opts = _lib.scan_opts2(window, window_lines)
+            _lib.check(L.tsg_scan_batch_device_opts2(self.engine(), ctypes.c_void_p(d_data.data_ptr()), off.ctypes.data,
+                                                     nfiles, cpaths, lens, b.ctypes.data, ctypes.byref(opts),
+                                                     ctypes.byref(res)))
+        elif h_data is None and window is not None:
             opts = _lib.scan_opts(window)
             _lib.check(L.tsg_scan_batch_device_opts(self.engine(), ctypes.c_void_p(d_data.data_ptr()), off.ctypes.data,
                                                     nfiles, cpaths, lens, b.ctypes.data, ctypes.byref(opts),
@@ -673,13 +686,14 @@ class Scanner:
                 stats = _lib.result_stats(res)
                 stats.update(_lib.result_gather_stats(res))
                 stats.update(_lib.result_gather_window_stats(res))
+                stats.update(_lib.result_gather_line_stats(res))
         finally:
             L.tsg_result_free(res)
         for s in out:
             s.pop("Error", None)
         return (out, stats) if with_stats else out
 
-    def ScanBatchDevice(self, d_data, offsets, paths, binary=None, with_stats=False, window=None):
+    def ScanBatchDevice(self, d_data, offsets, paths, binary=None, with_stats=False, window=None, window_lines=None):
         """The device-only scan (tsg_scan_batch_device): the batch exists only
         in HBM.  d_data: uint8 device tensor, the files packed back to back,
         16-byte aligned, with at least 16 bytes after the batch; offsets:
@@ -701,6 +715,15 @@ class Scanner:
         (tsg_result_gather_window_stats); gather_bytes counts everything that
         crossed.  None, or before = after = 0: whole files.
 
+        window_lines = cap (tsg_scan_batch_device_opts2, with window only):
+        each window grows to the lines the confirmer reads -- back to the
+        start of the line two above the candidate, on to the end of the line
+        below the match -- found on the GPU from the bytes and K1's newline
+        counts, each walk at most cap bytes long.  Small before / after then
+        do for every file whose lines are shorter than the cap.  with_stats
+        adds line_widened, line_capped and line_ms
+        (tsg_result_gather_line_stats).  0: the byte windows alone.
+
         The chain for files uploaded as read, of any kind (CRLF text, binaries
         to drop, binary .pyc files), is PrepareBatchDevice -> ScanBatchDevice,
         the device twin of PrepareBatch -> ScanBatch:
@@ -714,7 +737,9 @@ class Scanner:
 
             dst, new_off, total, _ = sc.StripCR(d_raw, d_raw_offsets, nfiles, raw_total)
             found = sc.ScanBatchDevice(dst, new_off.cpu().numpy(), paths)"""
-        return self._scan_device_tensor(d_data, offsets, paths, binary, None, with_stats, window)
+        if window_lines is not None and window is None:
+            raise ValueError("window_lines needs window=(before, after, min_file)")
+        return self._scan_device_tensor(d_data, offsets, paths, binary, None, with_stats, window, window_lines)
 
     def ScanBatchResident(self, d_data, h_data, offsets, paths, binary=None, with_stats=False):
         """tsg_scan_batch_resident: as ScanBatchDevice, with the caller's host
@@ -1374,6 +1399,39 @@ def plan_gather_windows(offsets, cands, fflags, all_rules, windowable, chunk, wi
             "runs": runs[:nruns.value].copy(), "total": total.value}
 
 
+def plan_gather_lines(data, offsets, cands, fflags, all_rules, windowable, chunk, window, window_lines, lead=0):
+    """plan_gather_windows with a line cap (tsg_test_plan_gather_lines, csrc/gather.h
+    line_window on the frame's bytes `data`): the same dict plus "widened" and
+    "capped".  window_lines 0: plan_gather_windows' layout.  Tests only."""
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    nfiles = len(off) - 1
+    total_bytes = int(off[-1]) if nfiles else 0
+    d = np.frombuffer(bytes(data[:total_bytes]) or b"\0", dtype=np.uint8).copy() if not isinstance(data, np.ndarray) \
+        else np.ascontiguousarray(data, dtype=np.uint8)
+    if len(d) < total_bytes:
+        raise ValueError("data is shorter than the offsets say")
+    cf = np.array([c[0] for c in cands] or [0], np.uint32)
+    cr = np.array([c[1] for c in cands] or [0], np.uint32)
+    cs = np.array([c[2] for c in cands] or [0], np.uint64)
+    ff = np.ascontiguousarray(fflags if len(fflags) else [0], dtype=np.uint32)
+    wr = np.ascontiguousarray(windowable if len(windowable) else [0], dtype=np.uint8)
+    nchunks = (total_bytes + chunk - 1) // chunk
+    cls = np.zeros(max(nfiles, 1), np.uint8)
+    first = np.zeros(max(nfiles, 1), np.uint32)
+    marks = np.zeros(max(nchunks, 1), np.uint8)
+    runs = np.zeros((nchunks // 2 + 2, 3), np.uint64)
+    nruns, total = ctypes.c_size_t(), ctypes.c_uint64()
+    widened, capped = ctypes.c_uint64(), ctypes.c_uint64()
+    opts = _lib.scan_opts2(window, window_lines)
+    _lib.check(_lib.lib().tsg_test_plan_gather_lines(
+        d.ctypes.data, off.ctypes.data, nfiles, lead, cf.ctypes.data, cr.ctypes.data, cs.ctypes.data, len(cands),
+        ff.ctypes.data, 1 if all_rules else 0, wr.ctypes.data, len(windowable), chunk, ctypes.byref(opts),
+        cls.ctypes.data, first.ctypes.data, marks.ctypes.data, runs.ctypes.data, len(runs), ctypes.byref(nruns),
+        ctypes.byref(total), ctypes.byref(widened), ctypes.byref(capped)))
+    return {"cls": cls[:nfiles], "first_run": first[:nfiles], "marks": marks[:nchunks],
+            "runs": runs[:nruns.value].copy(), "total": total.value, "widened": widened.value, "capped": capped.value}
+
+
 def windowable_rows(scanner):
     """(one byte per row of the rule table, number of rules) (tsg_test_windowable_rows).  Tests only."""
     n, nr = ctypes.c_size_t(), ctypes.c_size_t()
@@ -1407,18 +1465,25 @@ def _window_segment(res, k):
             "insufficient": arr(rec.insufficient, ctypes.c_uint32, np.uint32, rec.ninsufficient).tolist()}
 
 
-def scan_device_model_windows(scanner, args_list, chunk, window):
-    """CPU model of the device-only scan with windows (tsg_scan_device_model_opts):
+def scan_device_model_windows(scanner, args_list, chunk, window, window_lines=None):
+    """CPU model of the device-only scan with windows (tsg_scan_device_model_opts;
+    with window_lines, a line cap, tsg_scan_device_model_opts2):
     (findings, gather record of the windowed round with "cls" and
     "insufficient", gather record of the fallback round, stats).  Tests only."""
     data, offsets = pack(args_list)
     paths, lens, _keep = _lib.pack_paths([a.FilePath for a in args_list])
     binary = np.array([1 if a.Binary else 0 for a in args_list] or [0], dtype=np.uint8)
     res = ctypes.c_void_p()
-    opts = _lib.scan_opts(window)
-    _lib.check(_lib.lib().tsg_scan_device_model_opts(scanner._rs, data.ctypes.data, offsets.ctypes.data, len(args_list),
-                                                     paths, lens, binary.ctypes.data, chunk, ctypes.byref(opts), None,
-                                                     None, ctypes.byref(res)))
+    if window_lines is not None:
+        opts = _lib.scan_opts2(window, window_lines)
+        _lib.check(_lib.lib().tsg_scan_device_model_opts2(scanner._rs, data.ctypes.data, offsets.ctypes.data,
+                                                          len(args_list), paths, lens, binary.ctypes.data, chunk,
+                                                          ctypes.byref(opts), None, None, ctypes.byref(res)))
+    else:
+        opts = _lib.scan_opts(window)
+        _lib.check(_lib.lib().tsg_scan_device_model_opts(scanner._rs, data.ctypes.data, offsets.ctypes.data,
+                                                         len(args_list), paths, lens, binary.ctypes.data, chunk,
+                                                         ctypes.byref(opts), None, None, ctypes.byref(res)))
     try:
         out = _lib.result_json(res)
         for s in out:
@@ -1427,6 +1492,8 @@ def scan_device_model_windows(scanner, args_list, chunk, window):
         rec.update(_window_segment(res, 0))
         stats = _lib.result_gather_stats(res)
         stats.update(_lib.result_gather_window_stats(res))
+        if window_lines is not None:
+            stats.update(_lib.result_gather_line_stats(res))
         ns = ctypes.c_size_t()
         _lib.check(_lib.lib().tsg_result_raw_segments(res, ctypes.byref(ns)))
         return out, rec, _gather_segment(res, 1) if ns.value > 1 else None, stats
@@ -1472,7 +1539,7 @@ def scan_device_model(scanner, args_list, chunk, with_gather=False):
         _lib.lib().tsg_result_free(res)
 
 
-def scan_device_raw(scanner, args_list, base=0, pad=16, tail=None, device="cuda:0", window=None):
+def scan_device_raw(scanner, args_list, base=0, pad=16, tail=None, device="cuda:0", window=None, window_lines=None):
     """tsg_scan_batch_device with the raw-output and keep-gather hooks on (they
     stay on for the scanner's engine).  The batch lies `base` bytes (a multiple
     of 16) above a 256-byte boundary of a device tensor that ends `pad` bytes
@@ -1482,7 +1549,9 @@ def scan_device_raw(scanner, args_list, base=0, pad=16, tail=None, device="cuda:
     info["gather_stats"].  window: tsg_scan_batch_device_opts' windows; each
     segment's "gather" then also holds "cls" and "insufficient",
     info["gather_stats"] the window stats and info["fallback"] the fallback
-    round's gather record over the batch (None: no file fell back).  Tests only."""
+    round's gather record over the batch (None: no file fell back).
+    window_lines: the line cap (tsg_scan_batch_device_opts2); the line stats
+    then join info["gather_stats"].  Tests only."""
     import torch
     L = _lib.lib()
     data, offsets = pack(args_list)
@@ -1502,7 +1571,12 @@ def scan_device_raw(scanner, args_list, base=0, pad=16, tail=None, device="cuda:
     torch.cuda.synchronize()
     res = ctypes.c_void_p()
     try:
-        if window is not None:
+        if window_lines is not None:
+            opts = _lib.scan_opts2(window, window_lines)
+            _lib.check(L.tsg_scan_batch_device_opts2(eng, ctypes.c_void_p(full.data_ptr() + base), offsets.ctypes.data,
+                                                     len(args_list), paths, lens, binary.ctypes.data, ctypes.byref(opts),
+                                                     ctypes.byref(res)))
+        elif window is not None:
             opts = _lib.scan_opts(window)
             _lib.check(L.tsg_scan_batch_device_opts(eng, ctypes.c_void_p(full.data_ptr() + base), offsets.ctypes.data,
                                                     len(args_list), paths, lens, binary.ctypes.data, ctypes.byref(opts),
@@ -1530,6 +1604,8 @@ def scan_device_raw(scanner, args_list, base=0, pad=16, tail=None, device="cuda:
                 "gather_stats": _lib.result_gather_stats(res)}
         if window is not None:
             info["gather_stats"].update(wst)
+            if window_lines is not None:
+                info["gather_stats"].update(_lib.result_gather_line_stats(res))
             info["fallback"] = _gather_segment(res, nseg) if nseg < ns.value else None
         return findings, _result_candidates(res), info
     finally:
